@@ -29,7 +29,11 @@ only the blocks after the hooked layer while its tokens equal the baseline's (te
 which also yields the ΔNLL), and decodes the full model only from its divergence point; the JSON
 "work" block reports how much of each happened.
 
-    python bench.py [--gpus N --steps K --warmup W]
+A plain run sets up, warms up, times its K steps and prints one JSON line.  ``--full`` adds the side measurements
+after the timed steps (``config2``, ``post_forcing``, ``lora``, ``lowrank`` in the JSON, null otherwise);
+``--dump-outputs DIR`` writes the last timed step's cell records as ``DIR/<name>.npy``.
+
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -41,6 +45,7 @@ import os
 import sys
 import time
 
+_T0 = time.perf_counter()
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
@@ -60,6 +65,12 @@ from taboo_brittleness_amd.runtime.tuning import enable_tuned_gemms, flush_tuned
 
 BASELINE_VALUE = 0.642   # measured HF-eager sweep cells/sec on 1x MI355X (tools/hf_eager_baseline.py)
 HF_BATCHED_VALUE = 38.5  # HF-eager with the 66 cells of a pair batched per generate (hf_batched_baseline.py)
+
+
+def _mark(info, label: str) -> None:
+    """Host-side progress mark on stderr (rank 0; no device sync): seconds since this process imported bench.py."""
+    if info.is_main:
+        print(f"[bench] {label} at {time.perf_counter() - _T0:.1f}s", file=sys.stderr, flush=True)
 
 
 def _host_rss_gb():
@@ -158,6 +169,7 @@ def sweep_bench(args, info, cfg, model, tok, sae, layer: int, P: int, E: int, C:
     runner.trie_decode = not args.no_trie_decode
     runner.skip_noop_spikes = not args.no_skip_noop
     templates = runner.build_pairs(cfg.words, cfg.prompts)
+    _mark(info, f"setup{tag}: runner built")
 
     def pairs_for(step: int):
         # pair instance g of the whole job (every rank and step its own): template g mod 30, replicate g div 30,
@@ -172,6 +184,7 @@ def sweep_bench(args, info, cfg, model, tok, sae, layer: int, P: int, E: int, C:
     # does not depend on its replicate; with P >= 30 every rank's first step holds every template)
     cur = pairs_for(0)
     runner.run_baselines(cur)
+    _mark(info, f"setup{tag}: first baselines")
     first = {}
     for p in cur:
         first.setdefault((p.word, p.pidx), p)
@@ -188,6 +201,7 @@ def sweep_bench(args, info, cfg, model, tok, sae, layer: int, P: int, E: int, C:
     resid = torch.cat([mine[k] for k in order_keys if k in mine], 0)
     sae.calibrate(resid)
     runner._score_pairs(cur)
+    _mark(info, f"setup{tag}: SAE calibration, latent scores")
     import hashlib
 
     calib = hashlib.sha256(sae.threshold.float().cpu().numpy().tobytes()).hexdigest()[:16]
@@ -270,9 +284,12 @@ def sweep_bench(args, info, cfg, model, tok, sae, layer: int, P: int, E: int, C:
         cur, res, dt = step(k, cur)
         gather_results(res.result())
         if info.is_main:
-            print(f"[bench{tag}] warmup step {k + 1}/{warmup} done", file=sys.stderr, flush=True)
+            print(f"[bench{tag}] warmup step {k + 1}/{warmup} done at {time.perf_counter() - _T0:.1f}s",
+                  file=sys.stderr, flush=True)
     finish_gathers()
     runner.precapture_graphs()          # one-time setup: every decode row-bucket graph
+    _mark(info, f"setup{tag}: decode graphs captured")
+    graphs0 = len(runner.gen._graphs)
     # everything allocated so far (model, tokenizer tables, caches) is long-lived: keep the cyclic GC from
     # rescanning it on every collection inside the timed steps (pauses the launch thread otherwise)
     gc.collect()
@@ -313,6 +330,7 @@ def sweep_bench(args, info, cfg, model, tok, sae, layer: int, P: int, E: int, C:
     if marks is not None:
         marks.append(("end", time.monotonic_ns()))
     mine = time.perf_counter() - t0
+    _mark(info, f"timed steps{tag} done")
     per_rank = [float(v) for v in D.all_gather_objects(mine, info)]
     elapsed = D.all_reduce_max(mine, info)
     total_cells = D.all_reduce_max(float(n_done), info) * info.world   # every rank does the same count
@@ -320,7 +338,55 @@ def sweep_bench(args, info, cfg, model, tok, sae, layer: int, P: int, E: int, C:
     ms = 1000.0 * elapsed / max(steps, 1)
     return {"value": value, "elapsed": elapsed, "ms": ms, "per_rank": per_rank, "n_done": n_done,
             "gathered_rows": gathered_rows, "calib_all": calib_all, "runner": runner, "cur": cur, "batch": batch,
-            "n_cells": n_cells, "marks": marks}
+            "n_cells": n_cells, "marks": marks, "last": done, "late_graphs": len(runner.gen._graphs) - graphs0}
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path: str, records, max_new: int) -> dict:
+    """``--dump-outputs DIR``: the cell records the last timed step returned to its caller (this rank's, in cell
+    order), as float64 / float32 arrays ``DIR/<name>.npy`` -- one row per cell.  Ids (tokens, top-k guesses) are
+    stored as floats (exact below 2^24) and padded with -1.  Everything a record holds is a function of the run's
+    arguments (seeded weights, SAE, prompts and random-latent controls), so two builds can be compared array by array.
+    Returns {name: shape}."""
+    import numpy as np
+
+    words = sorted({r["word"] for r in records})
+    methods = sorted({r["method"] for r in records})
+    n = len(records)
+    nd = max([len(r["decoy_probs"]) for r in records] + [0])
+    resp = np.full((n, max_new), -1.0, np.float32)
+    topk = np.full((n, 5), -1.0, np.float32)
+    decoy = np.zeros((n, nd), np.float64)
+    for i, r in enumerate(records):
+        ids = list(r["response_ids"])[:max_new]
+        resp[i, :len(ids)] = ids
+        tk = list(r["topk_ids"])[:5]
+        topk[i, :len(tk)] = tk
+        decoy[i, :len(r["decoy_probs"])] = r["decoy_probs"]
+    arrays = {
+        # which cell a row is: word / method (indices into the sorted names), prompt, budget, trial and the
+        # cell's 63-bit seed as its high and low 32 bits
+        "cell_key": np.array([[words.index(r["word"]), methods.index(r["method"]), r["prompt_idx"], r["budget"],
+                               r["trial"], r["seed"] >> 32, r["seed"] & 0xFFFFFFFF] for r in records],
+                             np.float64).reshape(n, 7),
+        "p_secret": np.array([[r["p_secret_mean"], r["p_secret_final"], r["p_secret_max"], r["p_secret_mean_base"]]
+                              for r in records], np.float64).reshape(n, 4),
+        "nll": np.array([[r["nll_edit"], r["nll_base"], r["delta_nll"], r["nll_self"]] for r in records],
+                        np.float64).reshape(n, 4),
+        "flags": np.array([[r["n_gen"], float(r["leak"]), float(r["secret_in_topk"])] for r in records],
+                          np.float64).reshape(n, 3),
+        "decoy_probs": decoy,
+        "topk_ids": topk,
+        "response_ids": resp,
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes"
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def model_cells(cfg, methods):
@@ -486,6 +552,13 @@ def main() -> None:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps also run the side measurements (config2, post_forcing, "
+                         "lora, lowrank; each can be skipped with its --no-... option).  Without it a run sets up, "
+                         "warms up, times its steps and prints the result line with those four entries null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the cell records the last timed step returned (rank 0's) as "
+                         "DIR/<name>.npy (float64 / float32, one row per cell; see dump_outputs)")
     ap.add_argument("--arch", default="gemma2-9b")
     ap.add_argument("--pairs-per-step", default="auto",
                     help="(word, prompt) pairs per step and GPU, x 66 cells each, or 'auto' (default): as many as fit "
@@ -537,7 +610,7 @@ def main() -> None:
                     help="do not queue the next step's teacher-forced tail behind this step's readout")
     ap.add_argument("--profile-steps", action="store_true", help="print per-phase timings per step")
     ap.add_argument("--post-forcing", action="store_true",
-                    help="(default) also time the post-edit postgame token forcing of the sweep's SAE settings, "
+                    help="(default with --full) also time the post-edit postgame token forcing of the sweep's SAE settings, "
                          "after the timed region (reported as 'post_forcing', outside the headline)")
     ap.add_argument("--no-post-forcing", action="store_true", help="skip the post-edit forcing side measurement")
     ap.add_argument("--no-config2", action="store_true",
@@ -566,6 +639,7 @@ def main() -> None:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
 
     info = D.init_distributed(args.backend)
+    _mark(info, "setup: imports, process group")
     assert info.world == args.gpus, f"--gpus {args.gpus} but the launcher started {info.world} rank(s)"
     if info.world > 1 and "OMP_NUM_THREADS" not in os.environ:
         # one rank per GPU on one node: each rank's host threads get its share of the cores (torch's default is
@@ -609,6 +683,7 @@ def main() -> None:
                                        seed=99, device=dev))
     tok = SyntheticTokenizer(vocab_size=spec.vocab_size)
     sae = JumpReLUSAE.random(spec.hidden, cfg.sae.d_sae, seed=7, device=dev)
+    _mark(info, "setup: model, tokenizer, SAE")
     layer = min(cfg.model.layer_idx, spec.layers - 1)
     C = max(0, args.carry_rows) if not args.no_layer_resume else 0
     from taboo_brittleness_amd.interp.prompts import hint_prompt_ids
@@ -637,6 +712,11 @@ def main() -> None:
     value, elapsed, ms, per_rank = R["value"], R["elapsed"], R["ms"], R["per_rank"]
     n_done, gathered_rows, calib_all, runner, cur, batch = (R["n_done"], R["gathered_rows"], R["calib_all"],
                                                             R["runner"], R["cur"], R["batch"])
+    late_graphs = R["late_graphs"]
+    dumped = None
+    if args.dump_outputs and info.is_main:
+        dumped = dump_outputs(args.dump_outputs, R["last"], args.max_new)
+        _mark(info, "outputs written")
     R = None                      # (the side sweeps release the runner: no other reference may keep it alive)
     peak_gb = round(torch.cuda.max_memory_reserved(dev) / 1e9, 1) if on_gpu else None   # of the timed steps
     if on_gpu:      # the peak as a fraction of the device: torch's reserved peak + what lives outside its allocator
@@ -645,7 +725,8 @@ def main() -> None:
     for k_ in ("total", "outside_torch"):
         mem_plan.pop(k_, None)
     config2 = None
-    side = info.world == 1          # the side measurements are single-GPU numbers: not repeated per scaling run
+    # the side measurements run with --full only, and are single-GPU numbers: not repeated per scaling run
+    side = args.full and info.world == 1
     if (args.post_forcing or not args.no_config2) and info.is_main and side:
         # the side measurements below run after the timed region: release the sweep's decode state first (its
         # KV / store / pair-KV buffers are most of the ~240 GB the timed steps hold)
@@ -775,6 +856,8 @@ def main() -> None:
                 "carried_cells_per_step": round(runner.stats["carried"] / max(1, args.steps), 1),
                 # timed steps whose teacher-forced tail was queued behind the previous step's readout
                 "pipelined_steps": runner.stats["staged"],
+                # decode graphs captured inside the timed steps (0: every graph they replayed was captured in setup)
+                "graphs_captured_in_steps": late_graphs,
                 # non-degeneracy of the random model: distinct tokens per baseline response, and the
                 # fraction of response tokens equal to their input token (a self-copying model is 1.0)
                 "peak_mem_gb": peak_gb,
@@ -785,6 +868,8 @@ def main() -> None:
                                                   for p in cur) / max(1, sum(len(p.gen_toks) - 1 for p in cur))), 3),
             },
         }
+        if dumped is not None:
+            out["dumped"] = {"dir": args.dump_outputs, "arrays": dumped}
         phase_marks = list(getattr(runner, "phase_marks", []))
         if side:
             # after the headline's records are taken: the multi-adapter and low-rank sweeps (each its own P, warmup
@@ -801,6 +886,7 @@ def main() -> None:
                 out["lowrank"] = side_sweep(args, info, cfg, model, tok, sae, layer, spec, "lowrank",
                                             ("proj_targeted", "proj_random"), args.lowrank_steps, 1, rel)
         print(json.dumps(out), flush=True)
+        _mark(info, "result line printed")
     marks_path = os.environ.get("TB_PHASE_MARKS")
     if marks_path and info.is_main:
         with open(marks_path, "w") as f:

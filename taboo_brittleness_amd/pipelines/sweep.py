@@ -162,10 +162,13 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
 
     def precapture_graphs(self) -> int:
         """Capture every decode row-bucket graph now (call after the first batch, once the edit plan
-        exists), so later batches never pay a capture."""
+        exists), so later batches never pay a capture.  With the prefix-trie decode on, a cell batch decodes
+        through the "lo" / "hi" graphs only (whole-step graphs serve the standalone baseline pass and a batch
+        in which no two rows share a key: those are captured when first needed), so only they are captured."""
         if self.gen is None or getattr(self, "_hook", None) is None:
             return 0
-        return self.gen.precapture({self.layer: [self._hook, self.capture]}, "sweep")
+        parts = ("lo", "hi") if self.trie_decode and self.gen._share is not None else None
+        return self.gen.precapture({self.layer: [self._hook, self.capture]}, "sweep", parts=parts)
 
     def _S_needed(self, pairs: Sequence[Pair]) -> int:
         return max(p.plen for p in pairs) + self.max_new + 1

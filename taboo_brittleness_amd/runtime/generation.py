@@ -447,10 +447,13 @@ class Generator:
                 "nll": self.out_nll.index_select(0, r).cpu().numpy()}
 
     @torch.no_grad()
-    def precapture(self, hooks, graph_key, sizes: Optional[Sequence[int]] = None) -> int:
+    def precapture(self, hooks, graph_key, sizes: Optional[Sequence[int]] = None,
+                   parts: Optional[Sequence[Optional[str]]] = None) -> int:
         """Capture the decode-step graph of every row bucket up front (one-time setup, so no capture
         lands inside a timed decode).  Rows are parked beyond the cache (``pos = S``: no KV or
-        residual writes, no edit matches) and the decode state is restored afterwards."""
+        residual writes, no edit matches) and the decode state is restored afterwards.  ``parts``: which
+        graphs of a bucket (None = the whole step, "lo" / "hi" = the halves of a prefix-trie step; default: all
+        the generator can replay) -- a graph left out is captured when a decode first needs it."""
         if not (self.use_graphs and graph_key is not None):
             return 0
         if sizes is None:
@@ -466,7 +469,7 @@ class Generator:
             self._share["src"].fill_(-1)
         n = 0
         for nb in sizes:
-            for part in ((None, "lo", "hi") if self._share is not None else (None,)):
+            for part in ((None, "lo", "hi") if self._share is not None else (None,)) if parts is None else parts:
                 if ((graph_key, nb) if part is None else (part, graph_key, nb)) not in self._graphs:
                     self._capture(hooks, graph_key, nb, part)
                     n += 1

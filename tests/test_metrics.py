@@ -8,7 +8,7 @@ from taboo_brittleness_amd.metrics import (any_pass_at_k, accuracy, bootstrap_ci
                                            global_majority_vote_at_k, grouped_bootstrap_ci, id_topk_scores,
                                            leak_rate, majority_at_k, pass_at_k, prompt_accuracy_at_k)
 
-REF = "/root/reference"
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference")   # copies of its files
 
 
 def test_primitives_basic():
@@ -36,14 +36,18 @@ def test_calculate_metrics_overall_is_unweighted_mean():
     assert m["overall"]["any_pass"] == pytest.approx(2 / 3)
 
 
-@pytest.mark.parametrize("path", [
-    "src/results/logit_lens/seed_42/top5_real/logit_lens_evaluation_results.json",
-    "src/results copy/logit_lens/seed_42/top5_real/logit_lens_evaluation_results.json",
-])
+# the reference's path of each result file (the test's id) -> its copy under tests/golden/reference/
+RESULT_FILES = {
+    "src/results/logit_lens/seed_42/top5_real/logit_lens_evaluation_results.json":
+        "results/logit_lens_evaluation_results.json",
+    "src/results copy/logit_lens/seed_42/top5_real/logit_lens_evaluation_results.json":
+        "results_copy/logit_lens_evaluation_results.json",
+}
+
+
+@pytest.mark.parametrize("path", list(RESULT_FILES))
 def test_reproduces_reference_result_files(path):
-    full = os.path.join(REF, path)
-    if not os.path.exists(full):
-        pytest.skip("reference not mounted")
+    full = os.path.join(REF, RESULT_FILES[path])
     d = json.load(open(full))
     words = [k for k in d if k != "overall"]
     preds = {w: d[w]["predictions"] for w in words}
@@ -66,9 +70,7 @@ def test_id_level_api_matches_notebook_semantics():
 
 
 def test_id_topk_scores_ship_reference_file():
-    full = os.path.join(REF, "results/ll_topk_ship.json")
-    if not os.path.exists(full):
-        pytest.skip("reference not mounted")
+    full = os.path.join(REF, "ll_topk_ship.json")
     d = json.load(open(full))
     s = id_topk_scores(d["guesses_by_prompt"], d["secret_id"])
     assert s["pass@k"] == pytest.approx(d["pass@k"])

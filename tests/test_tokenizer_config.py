@@ -1,18 +1,14 @@
 import os
 
-import pytest
-
 from taboo_brittleness_amd.config import apply_overrides, config_from_dict, load_config
 from taboo_brittleness_amd.interp.prompts import (contains_secret, find_model_response_start, hint_prompt_ids,
                                                  infer_secret_from_adapter_id, truncate_at_second_end_of_turn)
 from taboo_brittleness_amd.models.tokenizer import SyntheticTokenizer, render_chat, secret_token_id
 
-REF_CFG = "/root/reference/configs/default.yaml"
+REF_CFG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference", "default.yaml")
 
 
 def test_reference_yaml_loads_unchanged():
-    if not os.path.exists(REF_CFG):
-        pytest.skip("reference not mounted")
     c = load_config(REF_CFG)
     assert c.model.layer_idx == 31 and c.model.top_k == 5
     assert c.experiment.seed == 42 and c.experiment.max_new_tokens == 50

@@ -15,7 +15,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout
 echo PYTEST_OK; tail -2 $OUT/pytest_gpu.log
 timeout -k 10 180 python __graft_entry__.py smoke > $OUT/smoke.log 2>&1
 echo SMOKE_OK; tail -1 $OUT/smoke.log | cut -c1-300
-timeout -k 10 600 python bench.py "$@" > $OUT/bench.log 2>&1
+timeout -k 10 600 python bench.py --full "$@" > $OUT/bench.log 2>&1
 echo BENCH_OK; tail -1 $OUT/bench.log
 if [ $PROF = 1 ]; then
   cd /tmp && export TMPDIR=/tmp
