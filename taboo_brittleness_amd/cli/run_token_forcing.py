@@ -41,7 +41,7 @@ def main(argv=None):
             edit = {"kind": "sae", "latents": [int(x) for x in args.ablate_latents.split(",")],
                     "alpha": cfg.intervention.alpha}
         results[w] = run_forcing(cfg, st.model, st.tok, [w], args.mode, st.sae, st.layer, edit, dp=dp)
-    merged = {"mode": args.mode, "per_word": {w: r["metrics"][w] for w, r in results.items()},
+    merged = {"mode": args.mode, "ablation_mode": cfg.intervention.ablation_mode, "per_word": {w: r["metrics"][w] for w, r in results.items()},
               "rows": [row for r in results.values() for row in r["rows"]],
               "parallel": {"world": info.world, "tp": cfg.parallel.tp, "dp": dp_size}}
     from ..metrics import calculate_metrics

@@ -129,7 +129,10 @@ class InterventionCfg:
     budgets: List[int] = field(default_factory=lambda: [1, 2, 4, 8, 16, 32])   # EP:126
     random_trials: int = 10             # EP:128
     alpha: float = 1.0                  # 1 = zero the latent (EP:126); <1 = partial (EP:200)
-    ablation_mode: str = "error_preserving"   # or "reconstruct" (replace x by decode(a'))
+    # sae cells: "error_preserving" (x - alpha * sum_S a_j W_dec[j]: the SAE's reconstruction error stays in the
+    # stream) or "reconstruct" (EP:126 literally: x <- b_dec + sum_j s_j a_j W_dec[j], s_j = 1 - alpha on S; adds the
+    # pure-splice control cell ``sae_splice``; interp/edits.py).  Read by the sweep and the forcing pipelines.
+    ablation_mode: str = "error_preserving"
     ranks: List[int] = field(default_factory=lambda: [1, 2, 4, 8])             # EP:146
     proj_random_trials: int = 5         # EP:150
     score_over: str = "prompt"          # "prompt" (per prompt) or "word" (average over prompts)

@@ -96,6 +96,14 @@ void tb_lowrank_edit(uint16_t* h, uint16_t* x_next, const uint8_t* apply, const 
                      int mmax, const void* E, const void* Dm, int table_f32, const float* bias, const float* thr,
                      const float* pre_bias, float alpha, const uint16_t* w_next, float eps, int M, int D,
                      float* coef_out, hipStream_t st);
+// reconstruct-mode splice: flagged rows h <- bf16(b_dec + sum_{a_j != 0, ascending j} s_j a_j W_dec[j]) with
+// a = acts[src_row[row]] (src_row null: acts[row]; out of [0, n_act_rows): row untouched), x_next = RMSNorm(h)
+void tb_sae_splice_edit(uint16_t* h, uint16_t* x_next, const uint8_t* apply, const int32_t* src_row,
+                        const float* acts, int n_act_rows, int L, const int32_t* idx, const int32_t* cnt, int mmax,
+                        const void* Wdec, int table_f32, const float* b_dec, float alpha, const uint16_t* w_next,
+                        float eps, int M, int D, hipStream_t st);
+// rows[cap]: ascending indices of the set flags, -1 padded; inv[n] (optional): list position per row or -1
+void tb_flag_compact(const uint8_t* flags, int n, int32_t* rows, int cap, int32_t* inv, hipStream_t st);
 void tb_sae_decode_sparse(const float* acts, const void* Wdec, int table_f32, const float* b_dec, uint16_t* out_bf16,
                           float* out_f32, int M, int L, int D, hipStream_t st);
 void tb_latent_score(const float* acts, const float* p, const uint8_t* spike, const int32_t* seg, float* out,

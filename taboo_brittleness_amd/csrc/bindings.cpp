@@ -776,6 +776,66 @@ void lowrank_edit(torch::Tensor h, c10::optional<torch::Tensor> x_next, torch::T
                   optf(pre_bias), (float)alpha, wn, (float)eps, M, D, co, cur_stream());
 }
 
+// Reconstruct-mode splice (csrc/sae.hip): acts [R, L] fp32 activation rows, src_row [M] int32 (optional) the
+// activation row of every h row.
+void sae_splice_edit(torch::Tensor h, c10::optional<torch::Tensor> x_next, torch::Tensor apply,
+                     c10::optional<torch::Tensor> src_row, torch::Tensor acts, torch::Tensor idx, torch::Tensor cnt,
+                     torch::Tensor Wdec, c10::optional<torch::Tensor> b_dec, double alpha,
+                     c10::optional<torch::Tensor> w_next, double eps) {
+  IN_BF16(h); IN_U8(apply); IN_F32(acts); IN_I32(idx); IN_I32(cnt); CHECK_DEV(Wdec); CHECK_CONTIG(Wdec);
+  const bool f32 = Wdec.scalar_type() == at::kFloat;
+  TORCH_CHECK(f32 || Wdec.scalar_type() == at::kBFloat16, "sae_splice_edit: W_dec must be fp32 or bf16");
+  TORCH_CHECK(Wdec.dim() == 2 && acts.dim() == 2, "sae_splice_edit: W_dec [L, D], acts [R, L]");
+  const int D = h.size(-1), M = h.numel() / std::max<int64_t>(D, 1);
+  const int L = Wdec.size(0);
+  TORCH_CHECK(D % 8 == 0 && D <= 256 * 8 * 4, "sae_splice_edit: need D % 8 == 0 and D <= 8192");
+  TORCH_CHECK(Wdec.size(1) == D && acts.size(1) == L, "sae_splice_edit: W_dec / acts shapes");
+  TORCH_CHECK(acts.size(0) < (int64_t)1 << 31, "sae_splice_edit: too many activation rows");
+  TORCH_CHECK(apply.numel() == M && cnt.numel() == M, "sae_splice_edit: apply / cnt rows");
+  TORCH_CHECK(M > 0 && idx.numel() % M == 0, "sae_splice_edit: idx rows");
+  const int mmax = idx.numel() / M;
+  TORCH_CHECK(mmax >= 1 && mmax <= 256, "sae_splice_edit: mmax");
+  TORCH_CHECK(!b_dec.has_value() || !b_dec->defined() || b_dec->numel() == D, "sae_splice_edit: b_dec numel");
+  const int32_t* sr = nullptr;
+  if (src_row.has_value() && src_row->defined()) {
+    IN_I32((*src_row));
+    TORCH_CHECK(src_row->numel() == M, "sae_splice_edit: src_row rows");
+    sr = src_row->data_ptr<int32_t>();
+  } else {
+    TORCH_CHECK(acts.size(0) >= M, "sae_splice_edit: acts needs a row per h row without src_row");
+  }
+  uint16_t* xn = nullptr;
+  const uint16_t* wn = nullptr;
+  if (x_next.has_value() && x_next->defined()) {
+    IN_BF16((*x_next));
+    TORCH_CHECK(x_next->numel() == h.numel(), "sae_splice_edit: x_next shape");
+    TORCH_CHECK(w_next.has_value() && w_next->defined(), "x_next needs w_next");
+    IN_BF16((*w_next));
+    TORCH_CHECK(w_next->numel() == D, "sae_splice_edit: w_next numel");
+    xn = reinterpret_cast<uint16_t*>(x_next->data_ptr());
+    wn = reinterpret_cast<const uint16_t*>(w_next->data_ptr());
+  }
+  c10::DeviceGuard g(h.device());
+  tb_sae_splice_edit(bf(h), xn, reinterpret_cast<const uint8_t*>(apply.data_ptr()), sr, acts.data_ptr<float>(),
+                     (int)acts.size(0), L, idx.data_ptr<int32_t>(), cnt.data_ptr<int32_t>(), mmax, Wdec.data_ptr(),
+                     f32 ? 1 : 0, optf(b_dec), (float)alpha, wn, (float)eps, M, D, cur_stream());
+}
+
+// rows [cap] int32 <- ascending indices of the set flags (-1 padded); inv [n] int32 (optional) <- list position
+void flag_compact(torch::Tensor flags, torch::Tensor rows, c10::optional<torch::Tensor> inv) {
+  IN_U8(flags); IN_I32(rows);
+  TORCH_CHECK(flags.numel() < (int64_t)1 << 31 && rows.numel() < (int64_t)1 << 31, "flag_compact: sizes");
+  int32_t* ip = nullptr;
+  if (inv.has_value() && inv->defined()) {
+    IN_I32((*inv));
+    TORCH_CHECK(inv->numel() == flags.numel(), "flag_compact: inv has one entry per flag");
+    ip = inv->data_ptr<int32_t>();
+  }
+  c10::DeviceGuard g(flags.device());
+  tb_flag_compact(reinterpret_cast<const uint8_t*>(flags.data_ptr()), (int)flags.numel(), rows.data_ptr<int32_t>(),
+                  (int)rows.numel(), ip, cur_stream());
+}
+
 void sae_decode_sparse(torch::Tensor acts, torch::Tensor Wdec, c10::optional<torch::Tensor> b_dec,
                        c10::optional<torch::Tensor> out_bf16, c10::optional<torch::Tensor> out_f32) {
   IN_F32(acts); CHECK_DEV(Wdec); CHECK_CONTIG(Wdec);
@@ -1082,6 +1142,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lens_gemm", &lens_gemm);
   m.def("lowrank_edit", &lowrank_edit);
   m.def("sae_decode_sparse", &sae_decode_sparse);
+  m.def("sae_splice_edit", &sae_splice_edit);
+  m.def("flag_compact", &flag_compact);
   m.def("latent_score", &latent_score);
   m.def("attention_lds_bytes", &attention_lds_bytes);
   m.def("p2p_alloc", &p2p_alloc);

@@ -15,6 +15,10 @@
 //                   m ablated latents are ever encoded); with E = D = U rows,
 //                   f = id it is the projection-out x - U U^T x (EP:148).
 //  sae_decode_sparse  x_hat = sum_{a_j != 0} a_j W_dec[j] + b_dec (L0 ~ 76 of 16k)
+//  sae_splice_edit  reconstruct-mode ablation (EP:126 literal): per flagged row h <- bf16(b_dec + sum over the
+//                   active latents, ascending, of s_j a_j W_dec[j]), s_j = 1 - alpha on the ablated ones, then
+//                   x_next = RMSNorm(h); activations from a row map (fresh encodes or a per-pair table).
+//  flag_compact     [rows] uint8 flags -> row list of static capacity (-1 padded) + inverse map, no host sync.
 //  latent_score     score_j = mean_{t in spikes} a_j(t) * max(0, corr_t(a_j, p_secret))
 //                   per prompt segment (EP:118-124).
 #include "common.h"
@@ -315,6 +319,178 @@ __global__ void __launch_bounds__(256) sae_decode_sparse_kernel(const float* __r
   }
 }
 
+// --------------------------------------------------------------- splice edit
+// Reconstruct-mode ablation: per flagged row  h <- bf16(b_dec + sum_{a_j != 0, ascending j} s_j a_j W_dec[j]),
+// s_j = 1 - alpha for j in idx[row, :cnt[row]], else 1; then x_next = RMSNorm(h).  The activations come from
+// acts[src_row[row]] (src_row == nullptr: acts[row]), so fresh encodes and rows of a per-pair table share the
+// kernel.  One workgroup (256 threads) per row; D <= 256*8*VPT.  The term order is fixed (ascending latent id,
+// one fp32 chain per column), so a row's result does not depend on its batch.
+constexpr int SPL_CAP = 1024;   // active latents held in LDS; rows above it take the chunked path (same order)
+
+template <typename TT, int VPT>
+__global__ void __launch_bounds__(256) sae_splice_edit_kernel(
+    uint16_t* __restrict__ h, uint16_t* __restrict__ x_next, const uint8_t* __restrict__ apply,
+    const int32_t* __restrict__ src_row, const float* __restrict__ acts, int n_act_rows, int L,
+    const int32_t* __restrict__ idx, const int32_t* __restrict__ cnt, int mmax, const TT* __restrict__ Wdec,
+    const float* __restrict__ b_dec, float alpha, const uint16_t* __restrict__ w_next, float eps, int D) {
+  const int row = blockIdx.x;
+  if (!apply[row]) return;
+  const int sr = src_row ? src_row[row] : row;
+  if (sr < 0 || sr >= n_act_rows) return;          // no activation row for this flag: leave the row alone
+  __shared__ int a_idx[SPL_CAP];
+  __shared__ float a_val[SPL_CAP];
+  __shared__ int s_idx[SPL_CAP];
+  __shared__ float s_val[SPL_CAP];
+  __shared__ int abl[256];
+  __shared__ float red[16];
+  __shared__ int nact;
+  const int tid = threadIdx.x;
+  const int nvec = D >> 3;
+  const float* ar = acts + (size_t)sr * L;
+  const int m = max(0, min(cnt[row], min(mmax, 256)));
+  const float keep = 1.f - alpha;
+  if (tid == 0) nact = 0;
+  if (tid < m) abl[tid] = idx[(size_t)row * mmax + tid];
+  __syncthreads();
+  for (int j = tid; j < L; j += 256) {
+    const float a = ar[j];
+    if (a != 0.f) {
+      const int slot = atomicAdd(&nact, 1);
+      if (slot < SPL_CAP) { a_idx[slot] = j; a_val[slot] = a; }
+    }
+  }
+  __syncthreads();
+  const int n = nact;
+  float v[VPT][8];
+#pragma unroll
+  for (int s = 0; s < VPT; ++s) {
+    const int i = tid + s * 256;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) v[s][q] = (b_dec && i < nvec) ? b_dec[i * 8 + q] : 0.f;
+  }
+  if (n <= SPL_CAP) {
+    // rank sort by latent id (ids are unique) with the row's scale applied: s_val[k] = s_j * a_j
+    for (int k = tid; k < n; k += 256) {
+      const int j = a_idx[k];
+      int rank = 0;
+      for (int t = 0; t < n; ++t) rank += a_idx[t] < j;
+      bool ab = false;
+      for (int t = 0; t < m; ++t) ab |= abl[t] == j;
+      s_idx[rank] = j;
+      s_val[rank] = ab ? keep * a_val[k] : a_val[k];
+    }
+    __syncthreads();
+    for (int k = 0; k < n; ++k) {
+      const float c = s_val[k];
+      const TT* dr = Wdec + (size_t)s_idx[k] * D;
+#pragma unroll
+      for (int s = 0; s < VPT; ++s) {
+        const int i = tid + s * 256;
+        if (i < nvec) {
+          float df[8];
+          load8<TT>(dr + i * 8, df);
+#pragma unroll
+          for (int q = 0; q < 8; ++q) v[s][q] = fmaf(c, df[q], v[s][q]);
+        }
+      }
+    }
+  } else {
+    // more active latents than the LDS list holds (a badly calibrated SAE): chunks of SPL_CAP consecutive latents,
+    // each scaled in parallel and then accumulated in ascending id -- the same terms in the same order
+    for (int base = 0; base < L; base += SPL_CAP) {
+      __syncthreads();
+      for (int k = tid; k < SPL_CAP; k += 256) {
+        const int j = base + k;
+        const float a = j < L ? ar[j] : 0.f;
+        float c = a;
+        if (a != 0.f) {
+          bool ab = false;
+          for (int t = 0; t < m; ++t) ab |= abl[t] == j;
+          if (ab) c = keep * a;
+        }
+        s_idx[k] = a != 0.f;
+        s_val[k] = c;
+      }
+      __syncthreads();
+      for (int k = 0; k < SPL_CAP; ++k) {
+        if (!s_idx[k]) continue;
+        const float c = s_val[k];
+        const TT* dr = Wdec + (size_t)(base + k) * D;
+#pragma unroll
+        for (int s = 0; s < VPT; ++s) {
+          const int i = tid + s * 256;
+          if (i < nvec) {
+            float df[8];
+            load8<TT>(dr + i * 8, df);
+#pragma unroll
+            for (int q = 0; q < 8; ++q) v[s][q] = fmaf(c, df[q], v[s][q]);
+          }
+        }
+      }
+    }
+  }
+  uint16_t* hr = h + (size_t)row * D;
+  float ss = 0.f;
+#pragma unroll
+  for (int s = 0; s < VPT; ++s) {
+    const int i = tid + s * 256;
+    if (i < nvec) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) { v[s][q] = rbf(v[s][q]); ss += v[s][q] * v[s][q]; }
+      reinterpret_cast<uint4*>(hr)[i] = pack8(v[s]);
+    }
+  }
+  if (x_next == nullptr) return;
+  const float r = rsqrtf(block_sum(ss, red) / (float)D + eps);
+#pragma unroll
+  for (int s = 0; s < VPT; ++s) {
+    const int i = tid + s * 256;
+    if (i < nvec) {
+      float wf[8], o[8];
+      unpack8(reinterpret_cast<const uint4*>(w_next)[i], wf);
+#pragma unroll
+      for (int q = 0; q < 8; ++q) o[q] = v[s][q] * r * (1.f + wf[q]);
+      reinterpret_cast<uint4*>(x_next + (size_t)row * D)[i] = pack8(o);
+    }
+  }
+}
+
+// -------------------------------------------------------------- flag compact
+// rows[0 .. count) = the indices i < n with flags[i] != 0 in ascending order, rows[count .. cap) = -1; inv[i]
+// (optional) = the list position of row i, -1 if unflagged.  Flags past the capacity are dropped (inv = -1), never
+// written out of range.  One workgroup of 1024 threads walks the flags in chunks with a running offset.
+__global__ void __launch_bounds__(1024) flag_compact_kernel(const uint8_t* __restrict__ flags, int n,
+                                                            int32_t* __restrict__ rows, int cap,
+                                                            int32_t* __restrict__ inv) {
+  __shared__ int wsum[16];
+  __shared__ int run;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  if (tid == 0) run = 0;
+  __syncthreads();
+  for (int base = 0; base < n; base += 1024) {
+    const int i = base + tid;
+    const bool f = i < n && flags[i] != 0;
+    const unsigned long long bal = __ballot(f);
+    const int before = __popcll(bal & ((1ull << lane) - 1ull));
+    if (lane == 0) wsum[wid] = __popcll(bal);
+    __syncthreads();
+    int off = run;
+    for (int w = 0; w < wid; ++w) off += wsum[w];
+    const int p = off + before;
+    if (f && p < cap) rows[p] = i;
+    if (inv != nullptr && i < n) inv[i] = (f && p < cap) ? p : -1;
+    __syncthreads();
+    if (tid == 0) {
+      int t = run;
+      for (int w = 0; w < 16; ++w) t += wsum[w];
+      run = t;
+    }
+    __syncthreads();
+  }
+  const int total = min(run, cap);
+  for (int p = total + tid; p < cap; p += 1024) rows[p] = -1;
+}
+
 // ------------------------------------------------------------- latent score
 // grid (ceil(L/256), G): segment g covers rows seg[g] .. seg[g+1]-1.
 __global__ void __launch_bounds__(256) latent_score_kernel(const float* __restrict__ acts,
@@ -391,6 +567,28 @@ void tb_sae_decode_sparse(const float* acts, const void* Wdec, int table_f32, co
   else
     hipLaunchKernelGGL(sae_decode_sparse_kernel<uint16_t>, dim3(M), dim3(256), 0, st, acts,
                        reinterpret_cast<const uint16_t*>(Wdec), b_dec, out_bf16, out_f32, L, D);
+}
+
+void tb_sae_splice_edit(uint16_t* h, uint16_t* x_next, const uint8_t* apply, const int32_t* src_row,
+                        const float* acts, int n_act_rows, int L, const int32_t* idx, const int32_t* cnt, int mmax,
+                        const void* Wdec, int table_f32, const float* b_dec, float alpha, const uint16_t* w_next,
+                        float eps, int M, int D, hipStream_t st) {
+  if (M <= 0) return;
+  const int nvec = D >> 3;
+#define TB_SPL(TT, VPT)                                                                                            \
+  hipLaunchKernelGGL((sae_splice_edit_kernel<TT, VPT>), dim3(M), dim3(256), 0, st, h, x_next, apply, src_row, acts, \
+                     n_act_rows, L, idx, cnt, mmax, (const TT*)Wdec, b_dec, alpha, w_next, eps, D)
+  if (table_f32) {
+    if (nvec <= 256) TB_SPL(float, 1); else if (nvec <= 512) TB_SPL(float, 2); else TB_SPL(float, 4);
+  } else {
+    if (nvec <= 256) TB_SPL(uint16_t, 1); else if (nvec <= 512) TB_SPL(uint16_t, 2); else TB_SPL(uint16_t, 4);
+  }
+#undef TB_SPL
+}
+
+void tb_flag_compact(const uint8_t* flags, int n, int32_t* rows, int cap, int32_t* inv, hipStream_t st) {
+  if (cap <= 0 && (inv == nullptr || n <= 0)) return;
+  hipLaunchKernelGGL(flag_compact_kernel, dim3(1), dim3(1024), 0, st, flags, n, rows, cap, inv);
 }
 
 void tb_latent_score(const float* acts, const float* p, const uint8_t* spike, const int32_t* seg, float* out,

@@ -10,9 +10,21 @@ An :class:`EditPlan` describes, per batch row (= sweep cell), *where* to edit
 Both are the same row-local low-rank update, so one HIP kernel
 (``ops.lowrank_edit``) serves a whole mixed batch; the hook only computes the
 per-row "is this a spike position" mask on the device, which keeps the decode
-step graph-capturable.  ``reconstruct`` mode replaces ``x`` by the SAE
-reconstruction with the ablated latents zeroed (EP:126 literal reading) and is
-handled by :class:`ReconstructEditHook`.
+step graph-capturable.
+
+``EditPlan.mode = "reconstruct"`` is the literal reading of EP:126 for the ``sae``
+cells: *encode, zero the selected latents, decode back and continue*,
+``x <- bf16(b_dec + sum_j s_j a_j(x) W_dec[j])`` with ``s_j = 1 - alpha`` on the
+ablated latents and 1 elsewhere.  The SAE's reconstruction error leaves the
+stream, so no flagged row is ever a no-op and a cell with nothing ablated
+(``cnt = 0``) is the *pure splice* control.  The hook encodes the flagged rows
+(``sae.encode``, one kernel family at every row count) and splices them with
+``ops.sae_splice_edit``; both are pure per-row functions with a fixed summation
+order, so a row gives the same bits alone, inside a decode bucket, or taken from
+a table of activations encoded earlier (:meth:`EditHook.use_table`).  Everything
+is static-shape and free of host syncs (``ops.flag_compact`` lists the flagged
+rows of a prefill on the device), so the hook sits inside the decode hipGraphs
+like the error-preserving one.  Projection cells are unchanged.
 """
 from __future__ import annotations
 
@@ -35,6 +47,11 @@ class EditPlan:
     cnt: torch.Tensor                    # [B] int32
     alpha: float = 1.0
     basis: Optional[torch.Tensor] = None   # [n_rows, D] fp32 table of orthonormal basis rows (proj cells)
+    mode: str = "error_preserving"         # sae cells: or "reconstruct" (splice the SAE reconstruction in)
+    any_position: bool = False             # some row edits at ALL_POSITIONS (bounds the flagged rows of a forward)
+
+    def __post_init__(self):
+        check_mode(self.mode)
 
     @property
     def B(self) -> int:
@@ -43,7 +60,7 @@ class EditPlan:
     @staticmethod
     def build(device, spikes: Sequence[Sequence[int]], kinds: Sequence[str], sel: Sequence[Sequence[int]],
               alpha: float = 1.0, basis: Optional[torch.Tensor] = None, kmax: Optional[int] = None,
-              mmax: Optional[int] = None) -> "EditPlan":
+              mmax: Optional[int] = None, mode: str = "error_preserving") -> "EditPlan":
         B = len(spikes)
         kmax = kmax or max(1, max((len(s) for s in spikes), default=1))
         mmax = mmax or max(1, max((len(s) for s in sel), default=1))
@@ -63,10 +80,18 @@ class EditPlan:
                 ix[b, : len(m)] = m
                 cn[b] = len(m)
         t = lambda a: torch.from_numpy(a).to(device)   # noqa: E731
-        return EditPlan(t(sp), t(kd), t(ix), t(cn), alpha, basis.to(device) if basis is not None else None)
+        return EditPlan(t(sp), t(kd), t(ix), t(cn), alpha, basis.to(device) if basis is not None else None, mode,
+                        bool((sp == ALL_POSITIONS).any()))
 
 
 ALL_POSITIONS = -2   # spike value that matches every (non-padding) position: position-agnostic edits
+ABLATION_MODES = ("error_preserving", "reconstruct")
+
+
+def check_mode(mode: str) -> str:
+    if mode not in ABLATION_MODES:
+        raise ValueError(f"intervention.ablation_mode must be one of {', '.join(ABLATION_MODES)}, not {mode!r}")
+    return mode
 
 
 def spike_mask(pos: torch.Tensor, spikes: torch.Tensor, B: int, T: int) -> torch.Tensor:
@@ -84,6 +109,16 @@ class EditHook:
         self.plan = plan
         self.sae = sae
         self._bufs = {}
+        self._table = None
+        if plan.mode == "reconstruct" and sae is not None and sae.d_in % 8:
+            raise ValueError("reconstruct mode needs a residual width that is a multiple of 8")
+
+    def use_table(self, acts: Optional[torch.Tensor], base: Optional[torch.Tensor] = None) -> None:
+        """Reconstruct mode: take the flagged rows' activations from ``acts [R, d_sae]`` (encoded earlier from
+        the very residuals this forward is fed, e.g. a pair's baseline residuals at its spikes) instead of
+        encoding them: the row of plan row ``b`` at its ``k``-th spike is ``acts[base[b] + k]`` (``base [B]``
+        int32, < 0: that plan row is left unedited).  ``use_table(None)`` returns to fresh encodes."""
+        self._table = None if acts is None else (acts, base)
 
     def _rows(self, B: int, T: int, device):
         # per stream: the sweep runs the ride-along decode and the teacher-forced tail concurrently
@@ -99,6 +134,11 @@ class EditHook:
                 "apply_proj": torch.empty(B * T, dtype=torch.uint8, device=device),
                 "coef": torch.zeros(B * T, mmax, dtype=torch.float32, device=device),
             }
+            if self.plan.mode == "reconstruct" and self.sae is not None:
+                b["src"] = torch.empty(B * T, dtype=torch.int32, device=device)
+                cap = self._capacity(B, T)
+                if cap < B * T:
+                    b["rows"] = torch.empty(cap, dtype=torch.int32, device=device)
             self._bufs[key] = b
         return b
 
@@ -116,7 +156,9 @@ class EditHook:
         r["apply_proj"].copy_(hit & (kind == 2))
         r["idx"].view(B, T, -1).copy_(pl.idx.index_select(0, sl).view(B, 1, -1).expand(B, T, -1))
         r["cnt"].view(B, T).copy_(pl.cnt.index_select(0, sl).view(B, 1).expand(B, T))
-        if self.sae is not None:
+        if self.sae is not None and pl.mode == "reconstruct":
+            self._splice(h, x, ctx, r, spikes)
+        elif self.sae is not None:
             s = self.sae
             ops.lowrank_edit(h, r["apply_sae"], r["idx"], r["cnt"], s.W_encT, s.W_dec, s.b_enc, s.threshold,
                              s.b_dec if s.apply_b_dec_to_input else None, pl.alpha, ctx.w_next, ctx.eps, x,
@@ -125,38 +167,39 @@ class EditHook:
             ops.lowrank_edit(h, r["apply_proj"], r["idx"], r["cnt"], pl.basis, pl.basis, None, None, None, 1.0,
                              ctx.w_next, ctx.eps, x, None)
 
+    def _capacity(self, B: int, T: int) -> int:
+        """Host-known bound on the flagged rows of a ``[B, T]`` forward: a sequence is edited at no more than its
+        plan row's K spike positions, or anywhere under ``ALL_POSITIONS``."""
+        K = int(self.plan.spikes.shape[1])
+        return B * T if self.plan.any_position else min(B * T, B * K)
+
+    def _splice(self, h, x, ctx, r, spikes) -> None:
+        """Reconstruct mode for the flagged ``sae`` rows: activations from the table set by :meth:`use_table`,
+        else encoded here -- the whole bucket when every row can be flagged (decode steps, ``ALL_POSITIONS``),
+        otherwise only the rows ``ops.flag_compact`` lists (a prefill of ``B * T`` rows edits at most ``B * K``)."""
+        B, T = ctx.B, ctx.T
+        pl, s = self.plan, self.sae
+        M = B * T
+        hv = h.view(M, -1)
+        src = r["src"]
+        if self._table is not None:
+            acts, base = self._table
+            k = (ctx.pos.view(B, T, 1) == spikes.view(B, 1, -1)).to(torch.int32).argmax(-1)      # first matching spike
+            b0 = base.index_select(0, ctx.slot.long()).view(B, 1)
+            r["src"].view(B, T).copy_(torch.where(b0 >= 0, b0 + k, torch.full_like(k, -1)))
+        elif "rows" in r:
+            ops.flag_compact(r["apply_sae"], r["rows"].numel(), rows=r["rows"], inv=r["src"])
+            acts = s.encode(hv.index_select(0, r["rows"].clamp_min(0).long()))
+        else:
+            acts, src = s.encode(hv), None            # row i of the bucket reads acts[i]
+        ops.sae_splice_edit(hv, r["apply_sae"], acts, r["idx"], r["cnt"], s.W_dec, s.b_dec, pl.alpha, ctx.w_next,
+                            ctx.eps, x.view(M, -1), src)
+
     def ablated_activation(self) -> Optional[torch.Tensor]:
         """Per-row activations of the ablated latents from the last call (diagnostics)."""
         for v in self._bufs.values():
             return v["coef"]
         return None
-
-
-class ReconstructEditHook:
-    """``x <- decode(a with a_S = 0)`` at spike rows (replaces x by the SAE reconstruction)."""
-
-    def __init__(self, plan: EditPlan, sae):
-        self.plan, self.sae = plan, sae
-
-    def __call__(self, h: torch.Tensor, x: torch.Tensor, ctx) -> None:
-        B, T = ctx.B, ctx.T
-        pl = self.plan
-        sl = ctx.slot.long()
-        hit = spike_mask(ctx.pos, pl.spikes.index_select(0, sl), B, T) & (
-            pl.kind.index_select(0, sl).view(B, 1).expand(B, T).reshape(-1) == 1)
-        rows = torch.nonzero(hit).flatten()
-        if rows.numel() == 0:
-            return
-        acts = self.sae.encode(h[rows])
-        seqs = sl[rows // T]
-        sel = pl.idx[seqs].long()
-        valid = torch.arange(sel.shape[1], device=h.device)[None, :] < pl.cnt[seqs][:, None]
-        # scale_j = 1 - alpha for the ablated latents of the row's cell, 1 elsewhere
-        src = torch.where(valid, torch.full(sel.shape, 1.0 - pl.alpha, device=h.device), torch.ones(sel.shape, device=h.device))
-        scale = torch.ones_like(acts).scatter_reduce_(1, torch.where(valid, sel, torch.zeros_like(sel)), src.to(acts.dtype), reduce="amin")
-        rec = self.sae.decode(acts * scale)
-        h[rows] = rec.to(h.dtype)
-        x[rows] = ops.rmsnorm(h[rows].contiguous(), ctx.w_next, ctx.eps)
 
 
 class CaptureHook:

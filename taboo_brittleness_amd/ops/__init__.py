@@ -1009,6 +1009,33 @@ def lowrank_edit(h, apply, idx, cnt, E, Dm, bias=None, thr=None, pre_bias=None, 
     return h
 
 
+def sae_splice_edit(h, apply, acts, idx, cnt, Wdec, b_dec=None, alpha=1.0, w_next=None, eps=1e-6, x_next=None,
+                    src_row=None):
+    """Reconstruct-mode SAE ablation, in place: per flagged row ``h <- bf16(b_dec + sum_{a_j != 0, ascending j}
+    s_j a_j Wdec[j])`` with ``a = acts[src_row[row]]`` (``src_row`` None: ``acts[row]``), ``s_j = 1 - alpha`` for
+    ``j`` in ``idx[row, :cnt[row]]`` and 1 elsewhere (fp32 accumulation in that order, so a row's bits do not
+    depend on its batch), then ``x_next = RMSNorm(h, w_next)``.  ``cnt == 0`` is the pure splice; unflagged rows
+    (and rows whose ``src_row`` is outside ``acts``) keep ``h`` and ``x_next`` bit for bit."""
+    if h.is_cuda:
+        _k().sae_splice_edit(h, x_next, apply, src_row, acts, idx, cnt, Wdec, b_dec, float(alpha), w_next, float(eps))
+        return h
+    ref.sae_splice_edit(h, apply, acts, idx, cnt, Wdec, b_dec, alpha, w_next, eps, x_next, src_row)
+    return h
+
+
+def flag_compact(flags, cap: int, rows=None, inv=None):
+    """``rows [cap]`` int32: the indices of the set entries of ``flags [n]`` (uint8), ascending, unused entries -1;
+    ``inv [n]`` int32 (optional output): each row's place in the list, -1 if unflagged.  Static shapes and no host
+    sync, so a hook inside a captured graph can encode only its flagged rows; ``cap`` must bound the flag count
+    (flags past it are dropped, ``inv`` -1).  Returns ``rows``."""
+    rows = _out(rows, (int(cap),), torch.int32, flags.device)
+    if flags.is_cuda:
+        _k().flag_compact(flags, rows, inv)
+        return rows
+    ref.flag_compact(flags, rows, inv)
+    return rows
+
+
 def sae_decode_sparse(acts, Wdec, b_dec=None, out_bf16=None, out_f32=None):
     if acts.is_cuda:
         M = acts.numel() // Wdec.shape[0]

@@ -323,6 +323,48 @@ def lowrank_edit(h: torch.Tensor, apply: torch.Tensor, idx: torch.Tensor, cnt: t
             x_next.view(-1, D)[r] = rmsnorm(hv[r:r + 1], w_next, eps)[0]
 
 
+def sae_splice_edit(h: torch.Tensor, apply: torch.Tensor, acts: torch.Tensor, idx: torch.Tensor, cnt: torch.Tensor,
+                    Wdec: torch.Tensor, b_dec: Optional[torch.Tensor] = None, alpha: float = 1.0,
+                    w_next: Optional[torch.Tensor] = None, eps: float = 1e-6, x_next: Optional[torch.Tensor] = None,
+                    src_row: Optional[torch.Tensor] = None) -> None:
+    """In place on h (and x_next) at the flagged rows: ``h = bf16(b_dec + sum_{a_j != 0} s_j a_j Wdec[j])``, the
+    terms added one by one in ascending ``j`` in fp32 (the kernel's order), ``s_j = 1 - alpha`` on the row's
+    ablated latents ``idx[row, :cnt[row]]``."""
+    D = h.shape[-1]
+    hv = h.view(-1, D)
+    M = hv.shape[0]
+    mmax = idx.numel() // M
+    iv = idx.view(M, mmax)
+    av = acts.view(-1, Wdec.shape[0])
+    keep = torch.tensor(1.0, dtype=torch.float32) - torch.tensor(float(alpha), dtype=torch.float32)
+    for r in torch.nonzero(apply.view(-1).bool()).flatten().tolist():
+        sr = int(src_row.view(-1)[r]) if src_row is not None else r
+        if sr < 0 or sr >= av.shape[0]:
+            continue
+        a = av[sr].float()
+        m = max(0, min(int(cnt.view(-1)[r]), mmax, 256))
+        s = torch.ones_like(a)
+        sel = iv[r, :m].long()
+        sel = sel[(sel >= 0) & (sel < a.numel())]
+        s[sel] = keep
+        c = a * s
+        o = b_dec.float().clone() if b_dec is not None else torch.zeros(D, dtype=torch.float32)
+        for j in torch.nonzero(a != 0).flatten().tolist():
+            o = o + c[j] * Wdec[j].float()
+        hv[r] = o.to(h.dtype)
+        if x_next is not None and w_next is not None:
+            x_next.view(-1, D)[r] = rmsnorm(hv[r:r + 1], w_next, eps)[0]
+
+
+def flag_compact(flags: torch.Tensor, rows: torch.Tensor, inv: Optional[torch.Tensor] = None) -> None:
+    nz = torch.nonzero(flags.view(-1) != 0).flatten()[: rows.numel()].to(torch.int32)
+    rows.fill_(-1)
+    rows[: nz.numel()] = nz
+    if inv is not None:
+        inv.fill_(-1)
+        inv.view(-1)[nz.long()] = torch.arange(nz.numel(), dtype=torch.int32)
+
+
 def sae_decode_sparse(acts: torch.Tensor, Wdec: torch.Tensor, b_dec: Optional[torch.Tensor] = None) -> torch.Tensor:
     out = acts.float() @ Wdec.float()
     if b_dec is not None:

@@ -30,6 +30,9 @@ from .sweep import METHODS, SweepRunner, summarize_cells
 
 def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info: Optional[D.DistInfo] = None,
               batch: Optional[int] = None, log=print) -> Dict:
+    from ..interp.edits import check_mode
+
+    check_mode(cfg.intervention.ablation_mode)          # an unknown mode fails before anything is built
     info = info or D.init_distributed(cfg.parallel.backend, cfg.runtime.device)
     tp_ctx, dp_rank, dp_size = None, info.rank, info.world
     if cfg.parallel.tp > 1:
@@ -103,7 +106,10 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
     summary: Dict = {} if forcing is None else {"forcing": forcing}   # every rank holds the gathered curves
     if info.is_main:
         allres = sorted([r for part in gathered for r in part], key=lambda r: r["cell_id"])
+        for r in allres:
+            r["ablation_mode"] = runner.ablation_mode
         summary = summarize_cells(allres, cfg.words, cfg.word_plurals)
+        summary["ablation_mode"] = runner.ablation_mode
         summary["baselines"] = [{
             "word": p.word, "prompt_idx": p.pidx, "n_gen": len(p.resp), "spikes": p.spikes_rel,
             "p_secret_mean": float(p.p_secret.mean()) if p.p_secret is not None and p.p_secret.size else 0.0,
@@ -114,7 +120,8 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
                              "cells_per_s": len(allres) / max(t_cells, 1e-9)}
         summary["config"] = {"layer": stack.layer, "arch": cfg.model.arch, "methods": list(methods),
                              "budgets": cfg.intervention.budgets, "ranks": cfg.intervention.ranks,
-                             "subspace": cfg.intervention.subspace, "pca_pool": cfg.intervention.pca_pool}
+                             "subspace": cfg.intervention.subspace, "pca_pool": cfg.intervention.pca_pool,
+                             "ablation_mode": runner.ablation_mode}
         if forcing is not None:
             summary["forcing"] = forcing
         os.makedirs(out_dir, exist_ok=True)

@@ -39,6 +39,13 @@ Layer resume (``_run_batch_resume``) adds three more exact reuse levels that res
   the edit kernel itself on the baseline's residuals (:meth:`SweepRunner._spike_activity`), so the cell's
   teacher-forced tail starts at its first effective spike (``plan["f"]``).
 
+``intervention.ablation_mode = reconstruct`` (the literal EP:126 reading: the residual at a spike is replaced by
+the SAE's reconstruction with the ablated latents scaled) keeps every level but the last: no spliced row is a
+no-op, so every ``sae`` cell's tail starts at its pair's first spike.  The tail's hooked-layer rows are the
+baseline's own residuals, so their SAE activations are encoded once per pair (``Pair.splice_acts``, K rows) and the
+tail splices from that table without encoding; only the decode steps of diverged cells encode fresh rows.  The mode
+adds one ``sae_splice`` cell per pair (budget 0, nothing ablated): the pure-splice control.
+
 Module layout: this module holds the runner's driver (construction, baselines, ``run_cells``) and the
 summaries; its methods are grouped by phase into mixins -- :mod:`.sweep_plan` (pair scoring, cells, edit bases
 and plans, prefetch), :mod:`.sweep_decode` (one batch through the decode: layer resume, prefix-trie keys,
@@ -57,7 +64,7 @@ import torch
 
 from .. import ops
 from ..interp import analysis as A
-from ..interp.edits import CaptureHook
+from ..interp.edits import CaptureHook, check_mode
 from ..interp.logit_lens import lens_packed, lens_readout, reference_exclusions
 from ..interp.prompts import hint_prompt_ids
 from ..models.tokenizer import secret_token_id
@@ -83,6 +90,9 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
         self.layer = cfg.model.layer_idx if layer is None else layer
         self.max_new = cfg.experiment.max_new_tokens if max_new is None else max_new
         self.iv = cfg.intervention
+        # sae cells: error-preserving ablation, or "reconstruct" (the residual replaced by the SAE reconstruction
+        # with the ablated latents scaled, interp/edits.py; adds the pure-splice control cell per pair)
+        self.ablation_mode = check_mode(self.iv.ablation_mode)
         self.exclusion = exclusion
         self.use_graphs = use_graphs
         self.prefix_share = cfg.runtime.prefix_share if prefix_share is None else prefix_share
@@ -101,7 +111,10 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
         self.tf_prefix = True
         self.stats: Dict[str, int] = {"cells": 0, "diverged": 0, "tf_rows": 0, "lens_rows": 0,
                                       "decode_row_steps": 0, "decode_rows_run": 0, "carried": 0, "staged": 0,
-                                      "decode_lo_rows_run": 0, "decode_lo_groups": 0, "lens_gemm_rows": 0}
+                                      "decode_lo_rows_run": 0, "decode_lo_groups": 0, "lens_gemm_rows": 0,
+                                      # reconstruct mode: spliced rows by activation source -- tail rows read from
+                                      # the per-pair table, decode rows of diverged cells encoded fresh
+                                      "splice_table_rows": 0, "splice_decode_rows": 0}
         # decode-tail carry-over (opt-in; needs ``batch`` to include ``carry_rows`` spare slots): once fewer
         # than ``carry_rows`` diverged cells still decode, the rest continue in the next batch's decode
         # (merged with its new rows) instead of running a long small-batch tail.  Records of carried cells

@@ -348,6 +348,8 @@ class DecodeMixin:
             self.stats["decode_row_steps"] += gen.last_rows[0]
             self.stats["decode_rows_run"] += gen.last_rows[1]
             carry_move = self._carry_out(plan, cell_pairs, batch, D, seg, nll_c, row_src, rsteps, ran, n_ride_rows)
+        if self.ablation_mode == "reconstruct" and self.sae is not None and nc:
+            self._splice_stats(plan, cell_pairs, tf, D_a, row_src, out, nr)
         self._tick("decode")
         # ---- ride-along baselines: full lens (with running sums for their future cells)
         if nr:
@@ -395,6 +397,25 @@ class DecodeMixin:
             self._carry_move_pending = None
         self._tick("results")
         return results
+
+    def _splice_stats(self, plan, cell_pairs, tf, D_a, row_src, out, nr: int) -> None:
+        """Reconstruct mode, host bookkeeping of where the spliced rows' activations came from: the tail rows at a
+        spike of an ``sae`` cell before its divergence read the per-pair table; a diverged cell's spikes from its
+        divergence ``D`` up to its last fed position were encoded fresh inside the decode."""
+        nc = len(cell_pairs)
+        sae_c = plan["kind"][:nc] == 1
+        sp = plan["spikes"][:nc].astype(np.int64)
+        rel = sp - np.asarray([p.plen for p in cell_pairs], np.int64)[:, None]
+        ok = (sp >= 0) & sae_c[:, None]
+        lim = np.where(D_a >= 0, D_a, tf["E"] + 1)                      # tail rows past the divergence are unused
+        self.stats["splice_table_rows"] += int((ok & (rel >= tf["f"][:, None]) & (rel < lim[:, None]) &
+                                                (rel <= tf["E"][:, None])).sum())
+        ng = np.zeros(nc, np.int64)
+        for j, src in enumerate(row_src):
+            if src[0] == "new" and out is not None:
+                ng[src[1]] = out.n_gen[nr + j]
+        self.stats["splice_decode_rows"] += int((ok & (D_a[:, None] >= 0) & (rel >= D_a[:, None]) &
+                                                 (rel <= ng[:, None] - 2)).sum())
 
     def _trie_keys(self, n_ride: int, rows: Sequence, pre_slot: np.ndarray, pre_lo: np.ndarray,
                    start: np.ndarray) -> Optional[np.ndarray]:

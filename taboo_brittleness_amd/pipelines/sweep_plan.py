@@ -15,7 +15,7 @@ import torch
 from .. import ops
 from ..interp import analysis as A
 from ..interp.edits import EditHook, EditPlan
-from .sweep_types import METHODS, Cell, NextBatch, Pair, _h2d
+from .sweep_types import METHODS, SPLICE_METHOD, Cell, NextBatch, Pair, _h2d
 
 
 class PlanMixin:
@@ -66,7 +66,41 @@ class PlanMixin:
         bounds = np.searchsorted(g_h, np.arange(len(live) + 1))
         for g, p in enumerate(live):
             p.active_pool = l_h[bounds[g]:bounds[g + 1]].astype(np.int64)
+        if self.ablation_mode == "reconstruct":
+            # the rows the teacher-forced tail splices are these very residuals at the spikes: keep their
+            # activations per pair (K rows), so the tail never encodes (no row is a no-op in this mode, so the
+            # activity table of the no-op spike skip is not needed either)
+            key, K, n0 = self._sae_key(), self.iv.spikes_k, 0
+            for g, p in enumerate(live):
+                k = len(p.spikes_rel[:K])
+                p.splice_acts = acts.index_select(0, sp_rows[n0:n0 + k]) if k else acts[:0]
+                p.splice_key = key
+                n0 += len(p.spikes_rel)
+            return
         self._spike_activity(live)
+
+    @torch.no_grad()
+    def _splice_table(self, upairs: Sequence[Pair]):
+        """Reconstruct mode: the per-step activation table of the teacher-forced tail -- each pair's activations at
+        its spikes (``Pair.splice_acts``, re-encoded here if the SAE changed since they were taken), concatenated;
+        returns ``(table [R, d_sae], first row per pair)``."""
+        key, K = self._sae_key(), self.iv.spikes_k
+        offs, parts, n = [], [], 0
+        for p in upairs:
+            k = len(p.spikes_rel[:K])
+            if p.splice_key != key or p.splice_acts is None or p.splice_acts.shape[0] != k:
+                rows = torch.tensor([min(max(t, 0), p.resid.shape[0] - 1) for t in p.spikes_rel[:K]],
+                                    dtype=torch.long, device=self.dev)
+                p.splice_acts = self.sae.encode(p.resid.index_select(0, rows)) if k else \
+                    torch.zeros(0, self.sae.d_sae, dtype=torch.float32, device=self.dev)
+                p.splice_key = key
+            offs.append(n)
+            parts.append(p.splice_acts)
+            n += k
+        tab = torch.cat(parts, 0) if len(parts) > 1 else parts[0]
+        if tab.shape[0] == 0:
+            tab = torch.zeros(1, self.sae.d_sae, dtype=torch.float32, device=self.dev)
+        return tab.contiguous(), offs
 
     @torch.no_grad()
     def _spike_activity(self, live: Sequence[Pair]) -> None:
@@ -113,6 +147,8 @@ class PlanMixin:
         base = self.cfg.experiment.seed
         for pi, p in enumerate(pairs):
             for meth in methods:
+                if meth == SPLICE_METHOD:
+                    continue                         # added below, once per pair, in reconstruct mode only
                 if meth.startswith("sae"):
                     if self.sae is None:
                         continue
@@ -125,6 +161,10 @@ class PlanMixin:
                         # a replicate > 0 (the bench's repeated pairs) draws its own random latent sets / subspaces
                         key = (base, p.word, p.pidx, meth, bud, t) + ((p.rep,) if p.rep else ())
                         cells.append(Cell(pi, meth, int(bud), t, A.cell_seed(*key)))
+            if self.ablation_mode == "reconstruct" and self.sae is not None and \
+                    any(meth.startswith("sae") for meth in methods):
+                key = (base, p.word, p.pidx, SPLICE_METHOD, 0, 0) + ((p.rep,) if p.rep else ())
+                cells.append(Cell(pi, SPLICE_METHOD, 0, 0, A.cell_seed(*key)))      # the pure-splice control
         return cells
 
     def _bases(self, pairs: Sequence[Pair]) -> Dict[str, torch.Tensor]:
@@ -196,7 +236,7 @@ class PlanMixin:
             ca = np.asarray(cis)
             if s_abs:
                 sp[ca, : len(s_abs)] = s_abs
-            rnd = [ci for ci in cis if cells[ci].kind == "sae" and cells[ci].method != "sae_targeted"]
+            rnd = [ci for ci in cis if cells[ci].kind == "sae" and cells[ci].method not in ("sae_targeted", SPLICE_METHOD)]
             if rnd:
                 got = A.random_latents_batch(self.sae.d_sae, [cells[ci].budget for ci in rnd],
                                              [cells[ci].seed for ci in rnd],
@@ -214,6 +254,8 @@ class PlanMixin:
                         ix[ci, :n] = tg[:n]
                         cn[ci] = n
                         kd[ci] = 1
+                    elif c.method == SPLICE_METHOD:
+                        kd[ci] = 1                   # nothing ablated (cnt 0): the row is spliced as it is
                 else:
                     if c.method == "proj_targeted":
                         bk = p.word if self.iv.pca_pool == "word" else "__all__"
@@ -255,8 +297,8 @@ class PlanMixin:
         cells, or no activity table).  Latents outside a pair's activity table count as active everywhere."""
         K = self.iv.spikes_k
         f = np.full(self.B, -1, np.int64)
-        if not self.skip_noop_spikes:
-            return f
+        if not self.skip_noop_spikes or self.ablation_mode == "reconstruct":
+            return f                            # reconstruct: R(h) != h at every spike, no cell is its baseline
         key = self._sae_key()
         for pi, cis in by_pair.items():
             p = pairs[pi]
@@ -325,7 +367,7 @@ class PlanMixin:
             t = lambda a: torch.from_numpy(a).to(dev)   # noqa: E731
             basis = torch.zeros(plan["rows"], self.D, dtype=torch.float32, device=dev) if self._with_basis else None
             self._plan = EditPlan(t(plan["spikes"]), t(plan["kind"]), t(plan["idx"]), t(plan["cnt"]), self.iv.alpha,
-                                  basis)
+                                  basis, self.ablation_mode)
             self._hook = EditHook(self._plan, self.sae)
         else:
             for f in ("spikes", "kind", "idx", "cnt"):

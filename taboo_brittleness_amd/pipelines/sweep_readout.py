@@ -455,6 +455,40 @@ class ReadoutMixin:
         tabs = [packed_blocks(chunk, rpb) for (_, _, chunk) in chunks]
         tab_off = np.concatenate([[0], np.cumsum([t.shape[0] for t in tabs])]).astype(np.int64)
         tab_d = _h2d(torch.cat(tabs, 0), dev).to(dev, non_blocking=True) if tabs else None
+        # reconstruct mode: the tail's hooked-layer rows are the pairs' baseline residuals (H), whose activations
+        # at the spikes were encoded once per pair -- the edit hook splices from that table, no encode per cell
+        splice = [hk for hk in hooks.get(self.layer, ()) if isinstance(hk, EditHook) and hk.sae is not None and
+                  hk.plan.mode == "reconstruct"]
+        if splice:
+            acts_tab, offs = self._splice_table([p for p, _ in ulist])
+            tb = np.full(int(splice[0].plan.spikes.shape[0]), -1, np.int32)
+            tb[:nc] = np.asarray(offs, np.int32)[up_a]
+            tb_d = up_(tb)
+            for hk in splice:
+                hk.use_table(acts_tab, tb_d)
+        try:
+            self._tf_chunks(chunks, streams, tab_d, tab_off, pos_d, slot_d, tgt_d, src_d, H, ws_rows, step, hooks,
+                            nxt, ns, nt)
+        finally:
+            for hk in splice:
+                hk.use_table(None)
+        if len(streams) > 1:
+            main.wait_stream(streams[1])
+        if dev.type == "cuda":
+            host = torch.empty(3, M, dtype=torch.float32, pin_memory=True)
+            host.copy_(outs, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(dev))
+        else:
+            host, ev = outs, None
+        res["_pending"] = (host, ev, M)
+        self._tick("tf_launched")
+        return res
+
+    def _tf_chunks(self, chunks, streams, tab_d, tab_off, pos_d, slot_d, tgt_d, src_d, H, ws_rows, step, hooks,
+                   nxt, ns, nt) -> None:
+        """The packed forwards + vocab heads of :meth:`_tf_launch`, chunk by chunk."""
+        m, dev = self.m, self.dev
         for ci, (c0, c1, chunk) in enumerate(chunks):
             st = streams[ci % len(streams)]
             with (torch.cuda.stream(st) if st is not None else _nullctx()):
@@ -484,18 +518,6 @@ class ReadoutMixin:
                     lg = m.logits(x[q0:min(Mp, q0 + step)])[: q1 - q0]
                     ops.decode_head(lg, m.spec.final_softcap, tgt_d[c0 + q0:c0 + q1], nxt[c0 + q0:c0 + q1],
                                     ns[c0 + q0:c0 + q1], nt[c0 + q0:c0 + q1])
-        if len(streams) > 1:
-            main.wait_stream(streams[1])
-        if dev.type == "cuda":
-            host = torch.empty(3, M, dtype=torch.float32, pin_memory=True)
-            host.copy_(outs, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(dev))
-        else:
-            host, ev = outs, None
-        res["_pending"] = (host, ev, M)
-        self._tick("tf_launched")
-        return res
 
     def _cell_result(self, c: Cell, p: Pair, n_gen: int, resp: List[int], probs: np.ndarray, topk_ids: List[int],
                      nll_edit: float, nll_self: float) -> dict:

@@ -10,6 +10,10 @@ import numpy as np
 import torch
 
 METHODS = ("sae_targeted", "sae_random", "proj_targeted", "proj_random")
+# reconstruct mode only (intervention.ablation_mode): the pure splice -- the residual replaced by the SAE's
+# reconstruction with nothing ablated (budget 0, one cell per pair), the control that separates "the SAE error was
+# dropped" from "these latents were removed"
+SPLICE_METHOD = "sae_splice"
 
 
 @dataclass
@@ -42,6 +46,10 @@ class Pair:
     act_ids: Optional[np.ndarray] = None
     act_mask: Optional[np.ndarray] = None
     act_key: Optional[tuple] = None                     # SAE parameter identity/versions the table was built with
+    # reconstruct mode: SAE activations [len(spikes_rel[:K]), d_sae] of the baseline residuals at the spikes (the
+    # rows the teacher-forced tail splices), and the SAE parameter key they were encoded under
+    splice_acts: Optional[torch.Tensor] = None
+    splice_key: Optional[tuple] = None
 
     @property
     def first_edit(self) -> int:

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from ..config import Config
-from ..interp.edits import ALL_POSITIONS, EditHook, EditPlan
+from ..interp.edits import ALL_POSITIONS, EditHook, EditPlan, check_mode
 from ..interp.prompts import contains_secret, conversation_ids, pregame_ids
 from ..metrics import calculate_metrics
 from ..runtime.generation import Generator
@@ -61,13 +61,14 @@ def first_word(text: str) -> str:
     return m.group(0).lower() if m else ""
 
 
-def _hooks_for(B: int, layer: int, sae, edit: Optional[Dict], device) -> Optional[Dict[int, list]]:
+def _hooks_for(B: int, layer: int, sae, edit: Optional[Dict], device,
+               mode: str = "error_preserving") -> Optional[Dict[int, list]]:
     if not edit:
         return None
     kinds = [edit.get("kind", "sae")] * B
     sel = [list(edit["latents"] if edit.get("kind", "sae") == "sae" else range(edit["basis"].shape[0]))] * B
     plan = EditPlan.build(device, [[ALL_POSITIONS]] * B, kinds, sel, alpha=edit.get("alpha", 1.0),
-                          basis=edit.get("basis"))
+                          basis=edit.get("basis"), mode=mode)
     return {layer: [EditHook(plan, sae if edit.get("kind", "sae") == "sae" else None)]}
 
 
@@ -113,6 +114,7 @@ def run_forcing(cfg: Config, model, tok, words: Sequence[str], mode: str = "post
     tf = cfg.token_forcing
     layer = cfg.model.layer_idx if layer is None else layer
     dev = model.device
+    amode = check_mode(cfg.intervention.ablation_mode)     # how an SAE edit acts (interp/edits.py)
     phrases = list(tf.phrases) if mode != "naive" else list(tf.naive_prompts)
     dp = dp or DPShard()
     all_keys = [(w, ph) for w in words for ph in phrases]
@@ -126,7 +128,7 @@ def run_forcing(cfg: Config, model, tok, words: Sequence[str], mode: str = "post
             for w in words:
                 histories[w].append({"role": "user", "content": turn})
                 rows.append(conversation_ids(tok, histories[w], add_generation_prompt=True))
-            hooks = _hooks_for(len(rows), layer, sae, edit, dev)
+            hooks = _hooks_for(len(rows), layer, sae, edit, dev, amode)
             replies = _generate(model, rows, tf.warmup_max_new_tokens, hooks)
             for w, r in zip(words, replies):
                 histories[w].append({"role": "assistant", "content": tok.decode(r)})
@@ -143,7 +145,7 @@ def run_forcing(cfg: Config, model, tok, words: Sequence[str], mode: str = "post
         rows.append(ids)
     comps_mine = []
     if rows:
-        hooks = _hooks_for(len(rows), layer, sae, edit, dev)
+        hooks = _hooks_for(len(rows), layer, sae, edit, dev, amode)
         comps_mine = _generate(model, rows, tf.max_new_tokens if mode != "naive" else cfg.experiment.max_new_tokens,
                                hooks, groups=[words.index(all_keys[i][0]) for i in mine])
     got = dp.gather({i: c for i, c in zip(mine, comps_mine)})
@@ -160,7 +162,7 @@ def run_forcing(cfg: Config, model, tok, words: Sequence[str], mode: str = "post
     metrics = calculate_metrics(preds, list(words), cfg.word_plurals)
     for w in words:
         metrics[w]["predictions"] = preds[w]
-    return {"mode": mode, "metrics": metrics, "rows": records,
+    return {"mode": mode, "ablation_mode": amode, "metrics": metrics, "rows": records,
             "success_rate": sum(r["success"] for r in records) / max(1, len(records))}
 
 
@@ -169,12 +171,13 @@ class _ForcingHooks:
     captured for the first chunk replay for every later chunk, warm-up turn and call (only the plan's contents
     change), instead of one capture per chunk."""
 
-    def __init__(self, device, rows: int, mmax: int, nbasis: int, D: int, layer: int, sae, alpha: float):
+    def __init__(self, device, rows: int, mmax: int, nbasis: int, D: int, layer: int, sae, alpha: float,
+                 mode: str = "error_preserving"):
         basis = torch.zeros(nbasis, D, dtype=torch.float32, device=device) if nbasis else None
         self.plan = EditPlan.build(device, [[ALL_POSITIONS]] * rows, ["none"] * rows, [[]] * rows, alpha=alpha,
-                                   basis=basis, kmax=1, mmax=mmax)
+                                   basis=basis, kmax=1, mmax=mmax, mode=mode)
         self.hooks = {layer: [EditHook(self.plan, sae)]}
-        self.sig = (rows, mmax, nbasis, D, layer, id(sae), float(alpha))
+        self.sig = (rows, mmax, nbasis, D, layer, id(sae), mode, float(alpha))
         self.rows = rows
 
     def fill(self, settings: Sequence[Dict], row_setting: Sequence[int]) -> bool:
@@ -235,7 +238,8 @@ def settings_alpha(settings: Sequence[Dict]) -> float:
     return al.pop() if al else 1.0
 
 
-def _forcing_state(model, rows: int, S: int, settings: Sequence[Dict], layer: int, sae) -> Dict:
+def _forcing_state(model, rows: int, S: int, settings: Sequence[Dict], layer: int, sae,
+                   mode: str = "error_preserving") -> Dict:
     mmax = max([len(st["latents"]) for st in settings if st.get("kind") == "sae"] + [1])
     nb = sum(int(st["basis"].shape[0]) for st in settings if st.get("kind") == "proj")
     alpha = settings_alpha(settings)
@@ -248,10 +252,10 @@ def _forcing_state(model, rows: int, S: int, settings: Sequence[Dict], layer: in
         ent = {"rows": rows, "S": S_alloc, "gen": Generator(model, rows, S_alloc, use_graphs=GRAPHS), "hooks": None}
         _FORCING_STATE[key] = ent
     h = ent["hooks"]
-    sig = (ent["rows"], mmax, nb, model.spec.hidden, layer, id(need_sae), alpha)
+    sig = (ent["rows"], mmax, nb, model.spec.hidden, layer, id(need_sae), mode, alpha)
     if h is None or h.sig[0] != sig[0] or h.sig[1] < mmax or h.sig[2] < nb or h.sig[3:] != sig[3:]:
         ent["hooks"] = _ForcingHooks(model.device, ent["rows"], max(mmax, h.sig[1] if h else 0),
-                                     max(nb, h.sig[2] if h else 0), model.spec.hidden, layer, need_sae, alpha)
+                                     max(nb, h.sig[2] if h else 0), model.spec.hidden, layer, need_sae, alpha, mode)
         ent["gen"].invalidate_graph()              # captured graphs hold the old plan's tensors
     return ent
 
@@ -300,6 +304,7 @@ def run_forcing_settings(cfg: Config, model, tok, settings: Sequence[Dict], mode
         return [got[i] for i in range(len(settings))]
     if not settings:
         return []
+    amode = check_mode(cfg.intervention.ablation_mode)     # SAE settings: error-preserving or reconstruct edits
     tf = cfg.token_forcing
     layer = cfg.model.layer_idx if layer is None else layer
     dev = model.device
@@ -320,7 +325,7 @@ def run_forcing_settings(cfg: Config, model, tok, settings: Sequence[Dict], mode
             reuse = ent0 is not None and ent0["S"] >= S and ent0["rows"] >= min(len(rows), FORCING_MAX_ROWS)
             chunk = min(len(rows), ent0["rows"]) if reuse else _auto_rows(model, len(rows), S)
         R = min(chunk, max(len(rows), 1))
-        ent = _forcing_state(model, R, S, settings, layer, sae)
+        ent = _forcing_state(model, R, S, settings, layer, sae, amode)
         gen, fh = ent["gen"], ent["hooks"]
         # the previous single-chunk call's prompts, still in the cache slots under the same edits (the warm-up turn
         # before this one): each row's new prompt re-prefills only what follows its longest common token prefix
@@ -393,4 +398,5 @@ def run_forcing_settings(cfg: Config, model, tok, settings: Sequence[Dict], mode
         res[si]["n"] += 1
     for r in res:
         r["success_rate"] = r["successes"] / max(1, r["n"])
+        r["ablation_mode"] = amode
     return res

@@ -88,6 +88,11 @@ def intervention_curves(summary: Dict, kind: str, path: str) -> None:
             ax.plot(xs, ys, "o-", color=col, label=meth)
             if lo is not None:
                 ax.fill_between(xs, lo, hi, color=col, alpha=0.2)
+        if kind == "sae":
+            # reconstruct mode: the pure splice (SAE reconstruction, nothing ablated) as a reference level
+            _, ys, _, _ = _curve(curves, "sae_splice", key)
+            if ys:
+                ax.axhline(ys[0], color="0.4", ls="--", lw=1, label="sae_splice (nothing ablated)")
         ax.set_xscale("log", base=2)
         ax.set_title(title)
         ax.set_xlabel("budget m" if kind == "sae" else "rank r")
