@@ -19,9 +19,14 @@ def main(argv=None):
     ap = parser(__doc__)
     ap.add_argument("--mode", default="postgame", choices=["pregame", "postgame", "naive"])
     ap.add_argument("--ablate-latents", default="", help="comma-separated SAE latents to ablate at every position")
+    ap.add_argument("--clamp-value", type=float, default=None,
+                    help="target of the latents under intervention.ablation_mode = clamp | steer "
+                         "(default: intervention.clamp_value)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     cfg, dev = setup(args)
+    if args.clamp_value is not None:
+        cfg.intervention.clamp_value = args.clamp_value
     info = D.init_distributed(cfg.parallel.backend, cfg.runtime.device)
     if info.world > 1:
         dev = info.device
@@ -41,7 +46,9 @@ def main(argv=None):
             edit = {"kind": "sae", "latents": [int(x) for x in args.ablate_latents.split(",")],
                     "alpha": cfg.intervention.alpha}
         results[w] = run_forcing(cfg, st.model, st.tok, [w], args.mode, st.sae, st.layer, edit, dp=dp)
-    merged = {"mode": args.mode, "ablation_mode": cfg.intervention.ablation_mode, "per_word": {w: r["metrics"][w] for w, r in results.items()},
+    merged = {"mode": args.mode, "ablation_mode": cfg.intervention.ablation_mode,
+              **({"clamp_value": r["clamp_value"] for r in results.values() if "clamp_value" in r}),
+              "per_word": {w: r["metrics"][w] for w, r in results.items()},
               "rows": [row for r in results.values() for row in r["rows"]],
               "parallel": {"world": info.world, "tp": cfg.parallel.tp, "dp": dp_size}}
     from ..metrics import calculate_metrics

@@ -131,8 +131,12 @@ class InterventionCfg:
     alpha: float = 1.0                  # 1 = zero the latent (EP:126); <1 = partial (EP:200)
     # sae cells: "error_preserving" (x - alpha * sum_S a_j W_dec[j]: the SAE's reconstruction error stays in the
     # stream) or "reconstruct" (EP:126 literally: x <- b_dec + sum_j s_j a_j W_dec[j], s_j = 1 - alpha on S; adds the
-    # pure-splice control cell ``sae_splice``; interp/edits.py).  Read by the sweep and the forcing pipelines.
+    # pure-splice control cell ``sae_splice``; interp/edits.py), or the two edits that push a latent towards
+    # ``clamp_value`` = c instead of removing it: "clamp" (a_j <- (1 - alpha) a_j + alpha c: held at c at alpha = 1,
+    # firing or not; c = 0 is the error-preserving ablation) and "steer" (a_j <- a_j + c, alpha ignored; c = 0 is
+    # rejected).  Read by the sweep and the forcing pipelines.
     ablation_mode: str = "error_preserving"
+    clamp_value: float = 0.0            # the target c of every selected latent in the clamp / steer modes
     ranks: List[int] = field(default_factory=lambda: [1, 2, 4, 8])             # EP:146
     proj_random_trials: int = 5         # EP:150
     score_over: str = "prompt"          # "prompt" (per prompt) or "word" (average over prompts)

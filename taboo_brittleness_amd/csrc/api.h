@@ -92,10 +92,11 @@ void tb_gemm4(const uint16_t* A, const uint16_t* W, void* C, const float* bias, 
               int ldc, int epi, int tile_rows, hipStream_t st, const uint16_t* a2 = nullptr, int k0 = 0);
 void tb_gemm_nt(const uint16_t* A, const uint16_t* W, void* C, const float* bias, const float* thr, int M, int N,
                 int K, int ldc, int epi, hipStream_t st);
+// val [M, mmax] fp32 (optional): latent_affine_edit, h += sum_j (val_j - alpha a_j) D_j; null: lowrank_edit
 void tb_lowrank_edit(uint16_t* h, uint16_t* x_next, const uint8_t* apply, const int32_t* idx, const int32_t* cnt,
                      int mmax, const void* E, const void* Dm, int table_f32, const float* bias, const float* thr,
                      const float* pre_bias, float alpha, const uint16_t* w_next, float eps, int M, int D,
-                     float* coef_out, hipStream_t st);
+                     float* coef_out, hipStream_t st, const float* val = nullptr);
 // reconstruct-mode splice: flagged rows h <- bf16(b_dec + sum_{a_j != 0, ascending j} s_j a_j W_dec[j]) with
 // a = acts[src_row[row]] (src_row null: acts[row]; out of [0, n_act_rows): row untouched), x_next = RMSNorm(h)
 void tb_sae_splice_edit(uint16_t* h, uint16_t* x_next, const uint8_t* apply, const int32_t* src_row,

@@ -731,10 +731,13 @@ void head_fused(torch::Tensor x, torch::Tensor W, torch::Tensor part, double cap
                  nll_self.data_ptr<float>(), np, M, N, K, cur_stream());
 }
 
-void lowrank_edit(torch::Tensor h, c10::optional<torch::Tensor> x_next, torch::Tensor apply, torch::Tensor idx,
-                  torch::Tensor cnt, torch::Tensor E, torch::Tensor Dm, c10::optional<torch::Tensor> bias,
-                  c10::optional<torch::Tensor> thr, c10::optional<torch::Tensor> pre_bias, double alpha,
-                  c10::optional<torch::Tensor> w_next, double eps, c10::optional<torch::Tensor> coef_out) {
+// lowrank_edit and, with val [M, mmax] fp32, latent_affine_edit (one kernel family, csrc/sae.hip)
+static void lowrank_edit_impl(torch::Tensor h, c10::optional<torch::Tensor> x_next, torch::Tensor apply,
+                              torch::Tensor idx, torch::Tensor cnt, torch::Tensor E, torch::Tensor Dm,
+                              c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> thr,
+                              c10::optional<torch::Tensor> pre_bias, double alpha,
+                              c10::optional<torch::Tensor> w_next, double eps,
+                              c10::optional<torch::Tensor> coef_out, const torch::Tensor* val) {
   IN_BF16(h); IN_U8(apply); IN_I32(idx); IN_I32(cnt); CHECK_DEV(E); CHECK_CONTIG(E); CHECK_DEV(Dm);
   CHECK_CONTIG(Dm);
   TORCH_CHECK(E.scalar_type() == Dm.scalar_type(), "E/D dtype mismatch");
@@ -745,6 +748,12 @@ void lowrank_edit(torch::Tensor h, c10::optional<torch::Tensor> x_next, torch::T
   TORCH_CHECK(D % 8 == 0 && D <= 256 * 8 * 4, "lowrank_edit: need D % 8 == 0 and D <= 8192");
   const int mmax = idx.numel() / M;
   TORCH_CHECK(mmax >= 1 && mmax <= 256, "lowrank mmax");
+  const float* vp = nullptr;
+  if (val != nullptr) {
+    IN_F32((*val));
+    TORCH_CHECK(val->numel() == (int64_t)M * mmax, "latent_affine_edit: val must be [rows, mmax] like idx");
+    vp = val->data_ptr<float>();
+  }
   TORCH_CHECK(!bias.has_value() || !bias->defined() || bias->numel() == E.size(0), "lowrank_edit: bias numel");
   TORCH_CHECK(!thr.has_value() || !thr->defined() || thr->numel() == E.size(0), "lowrank_edit: thr numel");
   TORCH_CHECK(!pre_bias.has_value() || !pre_bias->defined() || pre_bias->numel() == D, "lowrank_edit: pre_bias");
@@ -768,12 +777,29 @@ void lowrank_edit(torch::Tensor h, c10::optional<torch::Tensor> x_next, torch::T
   float* co = nullptr;
   if (coef_out.has_value() && coef_out->defined()) {
     IN_F32((*coef_out));
+    TORCH_CHECK(coef_out->numel() >= (int64_t)M * mmax, "lowrank_edit: coef_out smaller than [rows, mmax]");
     co = coef_out->data_ptr<float>();
   }
   c10::DeviceGuard g(h.device());
   tb_lowrank_edit(bf(h), xn, reinterpret_cast<const uint8_t*>(apply.data_ptr()), idx.data_ptr<int32_t>(),
                   cnt.data_ptr<int32_t>(), mmax, E.data_ptr(), Dm.data_ptr(), f32 ? 1 : 0, optf(bias), optf(thr),
-                  optf(pre_bias), (float)alpha, wn, (float)eps, M, D, co, cur_stream());
+                  optf(pre_bias), (float)alpha, wn, (float)eps, M, D, co, cur_stream(), vp);
+}
+
+void lowrank_edit(torch::Tensor h, c10::optional<torch::Tensor> x_next, torch::Tensor apply, torch::Tensor idx,
+                  torch::Tensor cnt, torch::Tensor E, torch::Tensor Dm, c10::optional<torch::Tensor> bias,
+                  c10::optional<torch::Tensor> thr, c10::optional<torch::Tensor> pre_bias, double alpha,
+                  c10::optional<torch::Tensor> w_next, double eps, c10::optional<torch::Tensor> coef_out) {
+  lowrank_edit_impl(h, x_next, apply, idx, cnt, E, Dm, bias, thr, pre_bias, alpha, w_next, eps, coef_out, nullptr);
+}
+
+// h += sum_j (val[row, j] - alpha a_j) Dm[idx_j] on the flagged rows (a_j as lowrank_edit computes it)
+void latent_affine_edit(torch::Tensor h, c10::optional<torch::Tensor> x_next, torch::Tensor apply, torch::Tensor idx,
+                        torch::Tensor cnt, torch::Tensor val, torch::Tensor E, torch::Tensor Dm,
+                        c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> thr,
+                        c10::optional<torch::Tensor> pre_bias, double alpha, c10::optional<torch::Tensor> w_next,
+                        double eps, c10::optional<torch::Tensor> coef_out) {
+  lowrank_edit_impl(h, x_next, apply, idx, cnt, E, Dm, bias, thr, pre_bias, alpha, w_next, eps, coef_out, &val);
 }
 
 // Reconstruct-mode splice (csrc/sae.hip): acts [R, L] fp32 activation rows, src_row [M] int32 (optional) the
@@ -1141,6 +1167,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("head_fused", &head_fused);
   m.def("lens_gemm", &lens_gemm);
   m.def("lowrank_edit", &lowrank_edit);
+  m.def("latent_affine_edit", &latent_affine_edit);
   m.def("sae_decode_sparse", &sae_decode_sparse);
   m.def("sae_splice_edit", &sae_splice_edit);
   m.def("flag_compact", &flag_compact);

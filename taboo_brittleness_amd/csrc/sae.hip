@@ -14,6 +14,8 @@
 //                   it is the error-preserving SAE latent ablation (EP:126; only the
 //                   m ablated latents are ever encoded); with E = D = U rows,
 //                   f = id it is the projection-out x - U U^T x (EP:148).
+//  latent_affine_edit  lowrank_edit with a per-row target: h += sum_j (val_j - alpha a_j) D_j, so a latent is
+//                   clamped (alpha = 1: held at val_j whether or not it fires) or steered (alpha = 0: val_j added).
 //  sae_decode_sparse  x_hat = sum_{a_j != 0} a_j W_dec[j] + b_dec (L0 ~ 76 of 16k)
 //  sae_splice_edit  reconstruct-mode ablation (EP:126 literal): per flagged row h <- bf16(b_dec + sum over the
 //                   active latents, ascending, of s_j a_j W_dec[j]), s_j = 1 - alpha on the ablated ones, then
@@ -146,14 +148,16 @@ __device__ __forceinline__ void load8<float>(const float* p, float* f) {
   f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
 }
 
-// One workgroup (256 threads) per row; D <= 256*8*VPT.
-template <typename TT, int VPT>
+// One workgroup (256 threads) per row; D <= 256*8*VPT.  AFF (latent_affine_edit): the row's coefficient becomes
+// alpha * a_j - val[row, j] = -delta_j, so h += sum_j delta_j D_j moves latent j from alpha * a_j to val_j.  The two
+// entry points share every other line, so val == 0 gives lowrank_edit's bits.
+template <typename TT, int VPT, bool AFF>
 __global__ void __launch_bounds__(256) lowrank_edit_kernel(
     uint16_t* __restrict__ h, uint16_t* __restrict__ x_next, const uint8_t* __restrict__ apply,
     const int32_t* __restrict__ idx, const int32_t* __restrict__ cnt, int mmax, const TT* __restrict__ E,
     const TT* __restrict__ Dm, const float* __restrict__ bias, const float* __restrict__ thr,
     const float* __restrict__ pre_bias, float alpha, const uint16_t* __restrict__ w_next, float eps, int D,
-    float* __restrict__ coef_out) {
+    float* __restrict__ coef_out, const float* __restrict__ val) {
   const int row = blockIdx.x;
   if (!apply[row]) return;
   __shared__ float red[16];
@@ -198,6 +202,11 @@ __global__ void __launch_bounds__(256) lowrank_edit_kernel(
     }
   }
   __syncthreads();
+  if (AFF) {
+    // alpha * a_j went through LDS as an fp32 value, so the subtraction cannot contract with the product
+    if (tid < m) coef[tid] -= val[(size_t)row * mmax + tid];
+    __syncthreads();
+  }
   // an all-zero edit (every ablated latent below its threshold here, or alpha = 0) is an exact no-op: h and
   // x_next stay bit-identical to the unedited forward (no re-rounded h, no re-normalised x)
   bool any = false;
@@ -544,17 +553,22 @@ void tb_gemm_nt(const uint16_t* A, const uint16_t* W, void* C, const float* bias
 void tb_lowrank_edit(uint16_t* h, uint16_t* x_next, const uint8_t* apply, const int32_t* idx, const int32_t* cnt,
                      int mmax, const void* E, const void* Dm, int table_f32, const float* bias, const float* thr,
                      const float* pre_bias, float alpha, const uint16_t* w_next, float eps, int M, int D,
-                     float* coef_out, hipStream_t st) {
+                     float* coef_out, hipStream_t st, const float* val) {
   if (M <= 0) return;
   const int nvec = D >> 3;
-#define TB_LR(TT, VPT)                                                                                          \
-  hipLaunchKernelGGL((lowrank_edit_kernel<TT, VPT>), dim3(M), dim3(256), 0, st, h, x_next, apply, idx, cnt, mmax, \
-                     (const TT*)E, (const TT*)Dm, bias, thr, pre_bias, alpha, w_next, eps, D, coef_out)
-  if (table_f32) {
-    if (nvec <= 256) TB_LR(float, 1); else if (nvec <= 512) TB_LR(float, 2); else TB_LR(float, 4);
+#define TB_LR(TT, VPT, AFF)                                                                                      \
+  hipLaunchKernelGGL((lowrank_edit_kernel<TT, VPT, AFF>), dim3(M), dim3(256), 0, st, h, x_next, apply, idx, cnt, \
+                     mmax, (const TT*)E, (const TT*)Dm, bias, thr, pre_bias, alpha, w_next, eps, D, coef_out, val)
+#define TB_LRV(TT, AFF)                                                                                  \
+  do {                                                                                                   \
+    if (nvec <= 256) TB_LR(TT, 1, AFF); else if (nvec <= 512) TB_LR(TT, 2, AFF); else TB_LR(TT, 4, AFF); \
+  } while (0)
+  if (val != nullptr) {
+    if (table_f32) TB_LRV(float, true); else TB_LRV(uint16_t, true);
   } else {
-    if (nvec <= 256) TB_LR(uint16_t, 1); else if (nvec <= 512) TB_LR(uint16_t, 2); else TB_LR(uint16_t, 4);
+    if (table_f32) TB_LRV(float, false); else TB_LRV(uint16_t, false);
   }
+#undef TB_LRV
 #undef TB_LR
 }
 

@@ -25,6 +25,20 @@ a table of activations encoded earlier (:meth:`EditHook.use_table`).  Everything
 is static-shape and free of host syncs (``ops.flag_compact`` lists the flagged
 rows of a prefill on the device), so the hook sits inside the decode hipGraphs
 like the error-preserving one.  Projection cells are unchanged.
+
+``EditPlan.mode = "clamp"`` and ``"steer"`` *push* the selected latents of the ``sae``
+cells towards per-row targets ``EditPlan.values`` (``c``, one per selected latent)
+instead of removing them (``ops.latent_affine_edit``, the sibling of the
+error-preserving kernel):
+
+* ``clamp`` -- ``a'_j = (1 - alpha) a_j + alpha c_j``: at ``alpha = 1`` the latent is held
+  at ``c_j`` whether or not it fires; ``c = 0`` is exactly the error-preserving ablation.
+* ``steer`` -- ``a'_j = a_j + c_j``: the feature is added regardless of the input.  The
+  plan's ``alpha`` is ignored in this mode.
+
+An inactive latent is edited too, so a flagged row is a no-op only where
+``alpha a_j == alpha c_j`` for every selected latent.  Same static shapes, no host
+sync; projection cells are unchanged.
 """
 from __future__ import annotations
 
@@ -49,9 +63,15 @@ class EditPlan:
     basis: Optional[torch.Tensor] = None   # [n_rows, D] fp32 table of orthonormal basis rows (proj cells)
     mode: str = "error_preserving"         # sae cells: or "reconstruct" (splice the SAE reconstruction in)
     any_position: bool = False             # some row edits at ALL_POSITIONS (bounds the flagged rows of a forward)
+    values: Optional[torch.Tensor] = None  # [B, mmax] fp32 targets c of the selected latents (clamp / steer modes)
 
     def __post_init__(self):
         check_mode(self.mode)
+        if self.mode in AFFINE_MODES and self.values is None:
+            self.values = torch.zeros(self.idx.shape, dtype=torch.float32, device=self.idx.device)
+        if self.values is not None and tuple(self.values.shape) != tuple(self.idx.shape):
+            raise ValueError(f"EditPlan.values must be [B, mmax] like idx {tuple(self.idx.shape)}, "
+                             f"not {tuple(self.values.shape)}")
 
     @property
     def B(self) -> int:
@@ -60,7 +80,9 @@ class EditPlan:
     @staticmethod
     def build(device, spikes: Sequence[Sequence[int]], kinds: Sequence[str], sel: Sequence[Sequence[int]],
               alpha: float = 1.0, basis: Optional[torch.Tensor] = None, kmax: Optional[int] = None,
-              mmax: Optional[int] = None, mode: str = "error_preserving") -> "EditPlan":
+              mmax: Optional[int] = None, mode: str = "error_preserving", values=None) -> "EditPlan":
+        """``values`` (clamp / steer modes): the targets of the selected latents, one scalar for all of them or a
+        per-row list of lists aligned with ``sel``."""
         B = len(spikes)
         kmax = kmax or max(1, max((len(s) for s in spikes), default=1))
         mmax = mmax or max(1, max((len(s) for s in sel), default=1))
@@ -80,17 +102,38 @@ class EditPlan:
                 ix[b, : len(m)] = m
                 cn[b] = len(m)
         t = lambda a: torch.from_numpy(a).to(device)   # noqa: E731
+        vals = None
+        if values is not None:
+            va = np.zeros((B, mmax), dtype=np.float32)
+            if isinstance(values, (int, float, np.number)):
+                va[:] = float(values)
+            else:
+                if len(values) != B:
+                    raise ValueError(f"EditPlan.build: values has {len(values)} rows, sel has {B}")
+                for b in range(B):
+                    if len(values[b]) != len(sel[b]):
+                        raise ValueError(f"EditPlan.build: values[{b}] has {len(values[b])} entries, "
+                                         f"sel[{b}] has {len(sel[b])}")
+                    n = min(len(values[b]), mmax)
+                    va[b, :n] = np.asarray(list(values[b])[:n], dtype=np.float32)
+            vals = t(va)
         return EditPlan(t(sp), t(kd), t(ix), t(cn), alpha, basis.to(device) if basis is not None else None, mode,
-                        bool((sp == ALL_POSITIONS).any()))
+                        bool((sp == ALL_POSITIONS).any()), vals)
 
 
 ALL_POSITIONS = -2   # spike value that matches every (non-padding) position: position-agnostic edits
-ABLATION_MODES = ("error_preserving", "reconstruct")
+ABLATION_MODES = ("error_preserving", "reconstruct", "clamp", "steer")
+AFFINE_MODES = ("clamp", "steer")      # sae cells pushed towards EditPlan.values (ops.latent_affine_edit)
 
 
-def check_mode(mode: str) -> str:
+def check_mode(mode: str, clamp_value: Optional[float] = None) -> str:
+    """The mode, validated; with ``clamp_value`` (the pipelines pass ``intervention.clamp_value``) also that a
+    ``steer`` run adds something."""
     if mode not in ABLATION_MODES:
         raise ValueError(f"intervention.ablation_mode must be one of {', '.join(ABLATION_MODES)}, not {mode!r}")
+    if mode == "steer" and clamp_value is not None and float(clamp_value) == 0.0:
+        raise ValueError("intervention.ablation_mode = steer needs a non-zero intervention.clamp_value "
+                         "(adding 0 leaves every cell at its baseline)")
     return mode
 
 
@@ -134,6 +177,8 @@ class EditHook:
                 "apply_proj": torch.empty(B * T, dtype=torch.uint8, device=device),
                 "coef": torch.zeros(B * T, mmax, dtype=torch.float32, device=device),
             }
+            if self.plan.mode in AFFINE_MODES:
+                b["val"] = torch.empty(B * T, mmax, dtype=torch.float32, device=device)
             if self.plan.mode == "reconstruct" and self.sae is not None:
                 b["src"] = torch.empty(B * T, dtype=torch.int32, device=device)
                 cap = self._capacity(B, T)
@@ -158,6 +203,15 @@ class EditHook:
         r["cnt"].view(B, T).copy_(pl.cnt.index_select(0, sl).view(B, 1).expand(B, T))
         if self.sae is not None and pl.mode == "reconstruct":
             self._splice(h, x, ctx, r, spikes)
+        elif self.sae is not None and pl.mode in AFFINE_MODES:
+            # clamp: alpha and val = fl32(alpha * c); steer: alpha = 0 and val = c (the plan's alpha is ignored)
+            s = self.sae
+            c = pl.values.index_select(0, sl)
+            alpha = pl.alpha if pl.mode == "clamp" else 0.0
+            r["val"].view(B, T, -1).copy_((c * alpha if pl.mode == "clamp" else c).view(B, 1, -1).expand(B, T, -1))
+            ops.latent_affine_edit(h, r["apply_sae"], r["idx"], r["cnt"], r["val"], s.W_encT, s.W_dec, s.b_enc,
+                                   s.threshold, s.b_dec if s.apply_b_dec_to_input else None, alpha, ctx.w_next,
+                                   ctx.eps, x, r["coef"])
         elif self.sae is not None:
             s = self.sae
             ops.lowrank_edit(h, r["apply_sae"], r["idx"], r["cnt"], s.W_encT, s.W_dec, s.b_enc, s.threshold,

@@ -1009,6 +1009,23 @@ def lowrank_edit(h, apply, idx, cnt, E, Dm, bias=None, thr=None, pre_bias=None, 
     return h
 
 
+def latent_affine_edit(h, apply, idx, cnt, val, E, Dm, bias=None, thr=None, pre_bias=None, alpha=1.0, w_next=None,
+                       eps=1e-6, x_next=None, coef_out=None):
+    """Latent clamping / steering, in place: per flagged row ``h <- bf16(h + sum_j delta_j Dm[idx_j])`` with
+    ``delta_j = val[row, j] - alpha * a_j`` and ``a_j = f(<h - pre_bias, E[idx_j]> + bias)`` as in
+    :func:`lowrank_edit` (``val [rows, mmax]`` fp32, aligned with ``idx``), then ``x_next = RMSNorm(h, w_next)``.
+    ``alpha = 1`` holds latent ``j`` at ``val_j`` whether or not it fires, ``alpha = 0`` adds ``val_j`` of it.  The
+    terms are added in slot order in fp32, so a row's bits do not depend on its batch; a row whose deltas are all
+    zero keeps ``h`` and ``x_next`` bit for bit; ``val == 0`` gives :func:`lowrank_edit`'s bits (the same device
+    code, csrc/sae.hip).  ``coef_out`` receives ``a_j``."""
+    if h.is_cuda:
+        _k().latent_affine_edit(h, x_next, apply, idx, cnt, val, E, Dm, bias, thr, pre_bias, float(alpha), w_next,
+                                float(eps), coef_out)
+        return h
+    ref.latent_affine_edit(h, apply, idx, cnt, val, E, Dm, bias, thr, pre_bias, alpha, w_next, eps, x_next, coef_out)
+    return h
+
+
 def sae_splice_edit(h, apply, acts, idx, cnt, Wdec, b_dec=None, alpha=1.0, w_next=None, eps=1e-6, x_next=None,
                     src_row=None):
     """Reconstruct-mode SAE ablation, in place: per flagged row ``h <- bf16(b_dec + sum_{a_j != 0, ascending j}

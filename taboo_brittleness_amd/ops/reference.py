@@ -323,6 +323,39 @@ def lowrank_edit(h: torch.Tensor, apply: torch.Tensor, idx: torch.Tensor, cnt: t
             x_next.view(-1, D)[r] = rmsnorm(hv[r:r + 1], w_next, eps)[0]
 
 
+def latent_affine_edit(h: torch.Tensor, apply: torch.Tensor, idx: torch.Tensor, cnt: torch.Tensor, val: torch.Tensor,
+                       E: torch.Tensor, Dm: torch.Tensor, bias=None, thr=None, pre_bias=None, alpha: float = 1.0,
+                       w_next: Optional[torch.Tensor] = None, eps: float = 1e-6,
+                       x_next: Optional[torch.Tensor] = None, coef_out: Optional[torch.Tensor] = None) -> None:
+    """``lowrank_edit`` towards a per-row target: ``h += sum_j delta_j Dm[idx_j]`` with ``delta_j = val[row, j] -
+    fl32(alpha * a_j)`` (the product rounded to fp32 before the subtraction), ``a_j`` as in :func:`lowrank_edit`.
+    Rows whose deltas are all zero are left untouched; ``val == 0`` is :func:`lowrank_edit` bit for bit."""
+    D = h.shape[-1]
+    hv = h.view(-1, D)
+    M = hv.shape[0]
+    mmax = idx.numel() // M
+    iv = idx.view(M, mmax)
+    vv = val.view(M, mmax).float()
+    for r in torch.nonzero(apply.view(-1).bool()).flatten().tolist():
+        m = max(0, min(int(cnt.view(-1)[r]), mmax, 256))
+        sel = iv[r, :m].long()
+        x = hv[r].float()
+        xb = x - pre_bias.float() if pre_bias is not None else x
+        pre = E[sel].float() @ xb
+        if bias is not None:
+            pre = pre + bias.float()[sel]
+        a = torch.where(pre > thr.float()[sel], pre, torch.zeros_like(pre)) if thr is not None else pre
+        if coef_out is not None:
+            coef_out.view(M, mmax)[r, :m] = a
+        c = alpha * a - vv[r, :m]         # = -delta: lowrank_edit's coefficient, so val = 0 shares its arithmetic
+        if not bool((c != 0).any()):
+            continue                      # all-zero edit: an exact no-op (h and x_next untouched)
+        newx = rbf(x - c @ Dm[sel].float())
+        hv[r] = newx.to(h.dtype)
+        if x_next is not None and w_next is not None:
+            x_next.view(-1, D)[r] = rmsnorm(hv[r:r + 1], w_next, eps)[0]
+
+
 def sae_splice_edit(h: torch.Tensor, apply: torch.Tensor, acts: torch.Tensor, idx: torch.Tensor, cnt: torch.Tensor,
                     Wdec: torch.Tensor, b_dec: Optional[torch.Tensor] = None, alpha: float = 1.0,
                     w_next: Optional[torch.Tensor] = None, eps: float = 1e-6, x_next: Optional[torch.Tensor] = None,

@@ -32,7 +32,8 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
               batch: Optional[int] = None, log=print) -> Dict:
     from ..interp.edits import check_mode
 
-    check_mode(cfg.intervention.ablation_mode)          # an unknown mode fails before anything is built
+    # an unknown mode (or a steer run that adds nothing) fails before anything is built
+    check_mode(cfg.intervention.ablation_mode, cfg.intervention.clamp_value)
     info = info or D.init_distributed(cfg.parallel.backend, cfg.runtime.device)
     tp_ctx, dp_rank, dp_size = None, info.rank, info.world
     if cfg.parallel.tp > 1:
@@ -108,8 +109,12 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
         allres = sorted([r for part in gathered for r in part], key=lambda r: r["cell_id"])
         for r in allres:
             r["ablation_mode"] = runner.ablation_mode
+            if runner.affine:                      # clamp / steer files only: the others stay byte-compatible
+                r["clamp_value"] = runner.clamp_value
         summary = summarize_cells(allres, cfg.words, cfg.word_plurals)
         summary["ablation_mode"] = runner.ablation_mode
+        if runner.affine:
+            summary["clamp_value"] = runner.clamp_value
         summary["baselines"] = [{
             "word": p.word, "prompt_idx": p.pidx, "n_gen": len(p.resp), "spikes": p.spikes_rel,
             "p_secret_mean": float(p.p_secret.mean()) if p.p_secret is not None and p.p_secret.size else 0.0,
@@ -122,6 +127,8 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
                              "budgets": cfg.intervention.budgets, "ranks": cfg.intervention.ranks,
                              "subspace": cfg.intervention.subspace, "pca_pool": cfg.intervention.pca_pool,
                              "ablation_mode": runner.ablation_mode}
+        if runner.affine:
+            summary["config"]["clamp_value"] = runner.clamp_value
         if forcing is not None:
             summary["forcing"] = forcing
         os.makedirs(out_dir, exist_ok=True)

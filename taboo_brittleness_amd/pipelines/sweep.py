@@ -46,6 +46,12 @@ baseline's own residuals, so their SAE activations are encoded once per pair (``
 tail splices from that table without encoding; only the decode steps of diverged cells encode fresh rows.  The mode
 adds one ``sae_splice`` cell per pair (budget 0, nothing ablated): the pure-splice control.
 
+``intervention.ablation_mode = clamp | steer`` push the selected latents towards ``intervention.clamp_value``
+(interp/edits.py) with the error-preserving run's cells, latent selection and seeds.  An inactive latent is edited
+too, so the no-op spike skip is off (every cell's tail starts at its pair's first spike and the activity table is
+not built); every other level stays on and exact, the edit being a pure per-row function of the very rows the tail
+feeds.
+
 Module layout: this module holds the runner's driver (construction, baselines, ``run_cells``) and the
 summaries; its methods are grouped by phase into mixins -- :mod:`.sweep_plan` (pair scoring, cells, edit bases
 and plans, prefetch), :mod:`.sweep_decode` (one batch through the decode: layer resume, prefix-trie keys,
@@ -64,7 +70,7 @@ import torch
 
 from .. import ops
 from ..interp import analysis as A
-from ..interp.edits import CaptureHook, check_mode
+from ..interp.edits import AFFINE_MODES, CaptureHook, check_mode
 from ..interp.logit_lens import lens_packed, lens_readout, reference_exclusions
 from ..interp.prompts import hint_prompt_ids
 from ..models.tokenizer import secret_token_id
@@ -91,8 +97,11 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
         self.max_new = cfg.experiment.max_new_tokens if max_new is None else max_new
         self.iv = cfg.intervention
         # sae cells: error-preserving ablation, or "reconstruct" (the residual replaced by the SAE reconstruction
-        # with the ablated latents scaled, interp/edits.py; adds the pure-splice control cell per pair)
-        self.ablation_mode = check_mode(self.iv.ablation_mode)
+        # with the ablated latents scaled, interp/edits.py; adds the pure-splice control cell per pair), or "clamp" /
+        # "steer": the selected latents pushed towards clamp_value (same cells, ops.latent_affine_edit)
+        self.ablation_mode = check_mode(self.iv.ablation_mode, self.iv.clamp_value)
+        self.affine = self.ablation_mode in AFFINE_MODES
+        self.clamp_value = float(self.iv.clamp_value)
         self.exclusion = exclusion
         self.use_graphs = use_graphs
         self.prefix_share = cfg.runtime.prefix_share if prefix_share is None else prefix_share

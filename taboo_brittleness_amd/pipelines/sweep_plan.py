@@ -77,6 +77,8 @@ class PlanMixin:
                 p.splice_key = key
                 n0 += len(p.spikes_rel)
             return
+        if self.affine:
+            return                              # clamp / steer edit inactive latents too: no spike is skipped
         self._spike_activity(live)
 
     @torch.no_grad()
@@ -297,8 +299,9 @@ class PlanMixin:
         cells, or no activity table).  Latents outside a pair's activity table count as active everywhere."""
         K = self.iv.spikes_k
         f = np.full(self.B, -1, np.int64)
-        if not self.skip_noop_spikes or self.ablation_mode == "reconstruct":
-            return f                            # reconstruct: R(h) != h at every spike, no cell is its baseline
+        if not self.skip_noop_spikes or self.ablation_mode == "reconstruct" or self.affine:
+            # reconstruct: R(h) != h at every spike, no cell is its baseline; clamp / steer: inactive latents move too
+            return f
         key = self._sae_key()
         for pi, cis in by_pair.items():
             p = pairs[pi]
@@ -366,8 +369,11 @@ class PlanMixin:
         if self._plan is None:
             t = lambda a: torch.from_numpy(a).to(dev)   # noqa: E731
             basis = torch.zeros(plan["rows"], self.D, dtype=torch.float32, device=dev) if self._with_basis else None
+            # clamp / steer: every selected latent has the same target, so the plan's values never change
+            values = torch.full(plan["idx"].shape, self.clamp_value, dtype=torch.float32, device=dev) \
+                if self.affine else None
             self._plan = EditPlan(t(plan["spikes"]), t(plan["kind"]), t(plan["idx"]), t(plan["cnt"]), self.iv.alpha,
-                                  basis, self.ablation_mode)
+                                  basis, self.ablation_mode, values=values)
             self._hook = EditHook(self._plan, self.sae)
         else:
             for f in ("spikes", "kind", "idx", "cnt"):

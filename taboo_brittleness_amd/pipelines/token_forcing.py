@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from ..config import Config
-from ..interp.edits import ALL_POSITIONS, EditHook, EditPlan, check_mode
+from ..interp.edits import AFFINE_MODES, ALL_POSITIONS, EditHook, EditPlan, check_mode
 from ..interp.prompts import contains_secret, conversation_ids, pregame_ids
 from ..metrics import calculate_metrics
 from ..runtime.generation import Generator
@@ -61,14 +61,24 @@ def first_word(text: str) -> str:
     return m.group(0).lower() if m else ""
 
 
+def setting_value(mode: str, st: Optional[Dict], default: float) -> Optional[float]:
+    """The clamp / steer target of an SAE setting or edit: its ``"value"``, else ``intervention.clamp_value``
+    (``default``); None in the other modes and for other kinds.  A ``steer`` edit that adds 0 is rejected."""
+    if mode not in AFFINE_MODES or not st or st.get("kind", "sae") != "sae":
+        return None
+    v = float(st.get("value", default))
+    check_mode(mode, v)
+    return v
+
+
 def _hooks_for(B: int, layer: int, sae, edit: Optional[Dict], device,
-               mode: str = "error_preserving") -> Optional[Dict[int, list]]:
+               mode: str = "error_preserving", value: Optional[float] = None) -> Optional[Dict[int, list]]:
     if not edit:
         return None
     kinds = [edit.get("kind", "sae")] * B
     sel = [list(edit["latents"] if edit.get("kind", "sae") == "sae" else range(edit["basis"].shape[0]))] * B
     plan = EditPlan.build(device, [[ALL_POSITIONS]] * B, kinds, sel, alpha=edit.get("alpha", 1.0),
-                          basis=edit.get("basis"), mode=mode)
+                          basis=edit.get("basis"), mode=mode, values=value)
     return {layer: [EditHook(plan, sae if edit.get("kind", "sae") == "sae" else None)]}
 
 
@@ -115,6 +125,7 @@ def run_forcing(cfg: Config, model, tok, words: Sequence[str], mode: str = "post
     layer = cfg.model.layer_idx if layer is None else layer
     dev = model.device
     amode = check_mode(cfg.intervention.ablation_mode)     # how an SAE edit acts (interp/edits.py)
+    cval = setting_value(amode, edit, cfg.intervention.clamp_value)   # clamp / steer: the latents' target
     phrases = list(tf.phrases) if mode != "naive" else list(tf.naive_prompts)
     dp = dp or DPShard()
     all_keys = [(w, ph) for w in words for ph in phrases]
@@ -128,7 +139,7 @@ def run_forcing(cfg: Config, model, tok, words: Sequence[str], mode: str = "post
             for w in words:
                 histories[w].append({"role": "user", "content": turn})
                 rows.append(conversation_ids(tok, histories[w], add_generation_prompt=True))
-            hooks = _hooks_for(len(rows), layer, sae, edit, dev, amode)
+            hooks = _hooks_for(len(rows), layer, sae, edit, dev, amode, cval)
             replies = _generate(model, rows, tf.warmup_max_new_tokens, hooks)
             for w, r in zip(words, replies):
                 histories[w].append({"role": "assistant", "content": tok.decode(r)})
@@ -145,7 +156,7 @@ def run_forcing(cfg: Config, model, tok, words: Sequence[str], mode: str = "post
         rows.append(ids)
     comps_mine = []
     if rows:
-        hooks = _hooks_for(len(rows), layer, sae, edit, dev, amode)
+        hooks = _hooks_for(len(rows), layer, sae, edit, dev, amode, cval)
         comps_mine = _generate(model, rows, tf.max_new_tokens if mode != "naive" else cfg.experiment.max_new_tokens,
                                hooks, groups=[words.index(all_keys[i][0]) for i in mine])
     got = dp.gather({i: c for i, c in zip(mine, comps_mine)})
@@ -162,8 +173,13 @@ def run_forcing(cfg: Config, model, tok, words: Sequence[str], mode: str = "post
     metrics = calculate_metrics(preds, list(words), cfg.word_plurals)
     for w in words:
         metrics[w]["predictions"] = preds[w]
-    return {"mode": mode, "ablation_mode": amode, "metrics": metrics, "rows": records,
-            "success_rate": sum(r["success"] for r in records) / max(1, len(records))}
+    out = {"mode": mode, "ablation_mode": amode, "metrics": metrics, "rows": records,
+           "success_rate": sum(r["success"] for r in records) / max(1, len(records))}
+    if cval is not None:
+        out["clamp_value"] = cval
+        for r in records:
+            r["ablation_mode"], r["clamp_value"] = amode, cval
+    return out
 
 
 class _ForcingHooks:
@@ -180,9 +196,12 @@ class _ForcingHooks:
         self.sig = (rows, mmax, nbasis, D, layer, id(sae), mode, float(alpha))
         self.rows = rows
 
-    def fill(self, settings: Sequence[Dict], row_setting: Sequence[int]) -> bool:
-        """Load the chunk's per-row edits; False when the chunk edits nothing (run it without hooks)."""
+    def fill(self, settings: Sequence[Dict], row_setting: Sequence[int], value: float = 0.0) -> bool:
+        """Load the chunk's per-row edits; False when the chunk edits nothing (run it without hooks).  Clamp / steer
+        modes: an SAE setting's target (``"value"``, default ``value``) goes into the plan's per-row ``values``, so
+        settings with different targets share a chunk (unlike ``alpha``)."""
         R, mmax = self.rows, int(self.plan.idx.shape[1])
+        va = np.zeros((R, mmax), dtype=np.float32) if self.plan.values is not None else None
         kd = np.zeros(R, dtype=np.int8)
         ix = np.zeros((R, mmax), dtype=np.int32)
         cn = np.zeros(R, dtype=np.int32)
@@ -195,6 +214,8 @@ class _ForcingHooks:
                 lat = list(st["latents"])
                 kd[i], cn[i] = 1, len(lat)
                 ix[i, :len(lat)] = lat
+                if va is not None:
+                    va[i, :len(lat)] = float(st.get("value", value))
             elif k == "proj":
                 U = st["basis"]
                 kd[i], cn[i] = 2, int(U.shape[0])
@@ -210,6 +231,8 @@ class _ForcingHooks:
         pl.kind.copy_(torch.from_numpy(kd))
         pl.idx.copy_(torch.from_numpy(ix))
         pl.cnt.copy_(torch.from_numpy(cn))
+        if va is not None:
+            pl.values.copy_(torch.from_numpy(va))
         if brow:
             pl.basis[:len(brow)].copy_(torch.stack([b.float() for b in brow]))
         return True
@@ -304,7 +327,9 @@ def run_forcing_settings(cfg: Config, model, tok, settings: Sequence[Dict], mode
         return [got[i] for i in range(len(settings))]
     if not settings:
         return []
-    amode = check_mode(cfg.intervention.ablation_mode)     # SAE settings: error-preserving or reconstruct edits
+    amode = check_mode(cfg.intervention.ablation_mode)     # SAE settings: how the edit acts (interp/edits.py)
+    cvals = [setting_value(amode, st if st.get("kind") == "sae" else None, cfg.intervention.clamp_value)
+             for st in settings]                           # clamp / steer: each SAE setting's target
     tf = cfg.token_forcing
     layer = cfg.model.layer_idx if layer is None else layer
     dev = model.device
@@ -334,7 +359,7 @@ def run_forcing_settings(cfg: Config, model, tok, settings: Sequence[Dict], mode
         single = len(rows) <= R
         for c0 in range(0, len(rows), R):
             chunk, cs = rows[c0:c0 + R], row_setting[c0:c0 + R]
-            edited = fh.fill(settings, cs)
+            edited = fh.fill(settings, cs, cfg.intervention.clamp_value)
             hooks, gk = (fh.hooks, "forcing") if edited else (None, "forcing_plain")
             if share and SHARE_PREFIX:                   # a setting's answers share its chat history
                 o = gen.generate_shared(chunk, cs, max_new, hooks=hooks, graph_key=gk)
@@ -399,4 +424,7 @@ def run_forcing_settings(cfg: Config, model, tok, settings: Sequence[Dict], mode
     for r in res:
         r["success_rate"] = r["successes"] / max(1, r["n"])
         r["ablation_mode"] = amode
+    for r, v in zip(res, cvals):
+        if v is not None:
+            r["clamp_value"] = v
     return res

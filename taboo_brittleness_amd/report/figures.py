@@ -74,6 +74,14 @@ def _curve(curves: List[Dict], method: str, key: str):
     return xs, [c[key] for _, c in pts], None, None
 
 
+def mode_label(summary: Dict) -> str:
+    """``"clamp, c = 4"`` for a sweep file of the clamp / steer modes (their ``sae`` cells push the latents towards
+    ``clamp_value``), ``""`` for the ablation modes."""
+    if "clamp_value" not in summary:
+        return ""
+    return f"{summary.get('ablation_mode', '?')}, c = {summary['clamp_value']:g}"
+
+
 def intervention_curves(summary: Dict, kind: str, path: str) -> None:
     curves = summary["curves"]
     tgt, rnd = f"{kind}_targeted", f"{kind}_random"
@@ -105,6 +113,8 @@ def intervention_curves(summary: Dict, kind: str, path: str) -> None:
     ax.set_xscale("log", base=2)
     ax.set_title("LL-Top-k Pass@10")
     axes[0].legend()
+    if kind == "sae" and mode_label(summary):
+        fig.suptitle(f"SAE latents: {mode_label(summary)}")
     plt.tight_layout()
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     fig.savefig(path, dpi=150)
@@ -125,6 +135,8 @@ def content_vs_inhibition(summary: Dict, path: str, forcing_delta: Optional[Dict
     ax.axhline(0, color="k", lw=0.5)
     ax.set_xlabel("Δ LL secret probability (content)")
     ax.set_ylabel("Δ token-forcing success" if forcing_delta else "leak rate (inhibition failure)")
+    if mode_label(summary):
+        ax.set_title(f"sae cells: {mode_label(summary)}")
     plt.tight_layout()
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     fig.savefig(path, dpi=150)
