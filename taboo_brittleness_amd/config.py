@@ -140,6 +140,11 @@ class InterventionCfg:
     ranks: List[int] = field(default_factory=lambda: [1, 2, 4, 8])             # EP:146
     proj_random_trials: int = 5         # EP:150
     score_over: str = "prompt"          # "prompt" (per prompt) or "word" (average over prompts)
+    # how the targeted latents are ranked: "corr" (EP:118-124: spike-mean activation x positive correlation with the
+    # secret probability), or by what ablating the latent alone does at the spikes: "effect_lens" (the exact drop of
+    # the secret's logit-lens logit, closed form through the final norm) / "attr_model" (first-order attribution
+    # alpha a_j (g . W_dec[j]) to the model's own secret logit; unsharded, merged weights); interp/analysis.py
+    latent_score: str = "corr"
     pca_pool: str = "word"              # pool spike residuals per "word" or across "all" models
     # targeted projection subspace (EP:144-146): "pca" of the spike residuals, or the gradient alternative
     # (EP:146): "grad_lens" (secret logit-lens logit through the final norm) / "grad_model" (the model's

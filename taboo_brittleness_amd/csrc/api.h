@@ -109,6 +109,13 @@ void tb_sae_decode_sparse(const float* acts, const void* Wdec, int table_f32, co
                           float* out_f32, int M, int L, int D, hipStream_t st);
 void tb_latent_score(const float* acts, const float* p, const uint8_t* spike, const int32_t* seg, float* out,
                      float* spike_mean, float* corr, int G, int L, hipStream_t st);
+// latent_effect.hip: causal latent scores at R spike rows.  eff [R, L] is written in full (0 where acts <= 0) and is
+// required (the segment mean reads it); score [G, L] (optional) = per-segment row mean.  mode 0: exact change of
+// the softcapped lens logit under the single-latent ablation x - alpha a_j W_dec[j]; mode 1: alpha a_j (v . W_dec[j]).
+// V is one row (v_per_row = 0) or one row per spike row.
+void tb_latent_effect(const float* acts, const uint16_t* X, const float* V, int v_per_row, const void* Wdec,
+                      int table_f32, const int32_t* seg, float* score, float* eff, int R, int G, int L, int D,
+                      double alpha, double eps, double cap, int mode, hipStream_t st);
 // p2p.hip
 int tb_p2p_header_bytes();
 int tb_p2p_max_ranks();

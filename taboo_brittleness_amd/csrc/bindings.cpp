@@ -900,6 +900,38 @@ void latent_score(torch::Tensor acts, torch::Tensor p, torch::Tensor spike, torc
                   seg.data_ptr<int32_t>(), out.data_ptr<float>(), sm, co, G, L, cur_stream());
 }
 
+// eff [R, L] (optional output): the per-row effects; without it the kernel's workspace comes from the caching
+// allocator here.  ``seg`` is ascending with seg[0] = 0 and seg[G] = R (the caller's contract; the kernel clamps).
+void latent_effect(torch::Tensor acts, torch::Tensor X, torch::Tensor V, torch::Tensor Wdec, torch::Tensor seg,
+                   torch::Tensor score, c10::optional<torch::Tensor> eff, double alpha, double eps, double cap,
+                   int64_t mode) {
+  IN_F32(acts); IN_BF16(X); IN_F32(V); CHECK_DEV(Wdec); CHECK_CONTIG(Wdec); IN_I32(seg); IN_F32(score);
+  const bool f32 = Wdec.scalar_type() == at::kFloat;
+  TORCH_CHECK(f32 || Wdec.scalar_type() == at::kBFloat16, "latent_effect: W_dec must be fp32 or bf16");
+  TORCH_CHECK(Wdec.dim() == 2 && acts.dim() == 2 && X.dim() == 2 && V.dim() == 2, "latent_effect: 2-d tensors");
+  const int64_t L = Wdec.size(0), D = Wdec.size(1), R = acts.size(0), G = seg.numel() - 1;
+  TORCH_CHECK(D % 8 == 0 && D <= 4096, "latent_effect: D must be a multiple of 8 and at most 4096, not ", D);
+  TORCH_CHECK(acts.size(1) == L, "latent_effect: acts last dim must equal W_dec rows");
+  TORCH_CHECK(X.size(0) == R && X.size(1) == D, "latent_effect: X must be [rows of acts, D]");
+  TORCH_CHECK(V.size(1) == D && (V.size(0) == 1 || V.size(0) == R), "latent_effect: V must be [1, D] or [R, D]");
+  TORCH_CHECK(G >= 0 && score.numel() == G * L, "latent_effect: score must be [len(seg) - 1, L]");
+  TORCH_CHECK(mode == 0 || mode == 1, "latent_effect: mode must be 0 (effect_lens) or 1 (attr_model)");
+  TORCH_CHECK(R * L < (int64_t)1 << 40, "latent_effect: rows x latents out of range");
+  torch::Tensor ws;
+  if (eff.has_value() && eff->defined()) {
+    IN_F32((*eff));
+    TORCH_CHECK(eff->numel() == R * L, "latent_effect: eff must be [R, L]");
+    ws = *eff;
+  } else {
+    ws = torch::empty({R, L}, acts.options());
+  }
+  c10::DeviceGuard g(acts.device());
+  tb_latent_effect(acts.data_ptr<float>(), reinterpret_cast<const uint16_t*>(X.data_ptr()), V.data_ptr<float>(),
+                   V.size(0) == 1 && R != 1 ? 0 : 1, Wdec.data_ptr(), f32 ? 1 : 0, seg.data_ptr<int32_t>(),
+                   score.data_ptr<float>(), ws.data_ptr<float>(), (int)R, (int)G, (int)L, (int)D, alpha, eps, cap,
+                   (int)mode, cur_stream());
+}
+
 int64_t attention_lds_bytes(int64_t hd) { return tb_attention_lds_bytes((int)hd); }
 
 // ---- one-shot P2P all-reduce (p2p.hip): regions are raw device pointers passed as int64
@@ -1172,6 +1204,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sae_splice_edit", &sae_splice_edit);
   m.def("flag_compact", &flag_compact);
   m.def("latent_score", &latent_score);
+  m.def("latent_effect", &latent_effect);
   m.def("attention_lds_bytes", &attention_lds_bytes);
   m.def("p2p_alloc", &p2p_alloc);
   m.def("p2p_free", &p2p_free);

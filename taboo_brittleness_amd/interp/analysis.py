@@ -58,6 +58,48 @@ def latent_scores(sae, resid_rows: torch.Tensor, p_secret: torch.Tensor, spike_r
     return score
 
 
+LATENT_SCORES = ("corr", "effect_lens", "attr_model")
+
+
+def check_latent_score(name: str) -> str:
+    """The ``intervention.latent_score`` selector, validated."""
+    if name not in LATENT_SCORES:
+        raise ValueError(f"intervention.latent_score must be one of {', '.join(LATENT_SCORES)}, not {name!r}")
+    return name
+
+
+@torch.no_grad()
+def latent_effects(sae, model, spike_rows: torch.Tensor, spike_acts: torch.Tensor, seg: Sequence[int],
+                   secret_ids: Sequence[int], alpha: float, mode: str, grads: Optional[torch.Tensor] = None,
+                   want_eff: bool = False):
+    """Causal latent scores per prompt segment, ``[G, d_sae]`` fp32 (``ops.latent_effect``): the mean over the
+    segment's spike rows of what ablating latent ``j`` alone (``x - alpha a_j W_dec[j]``) does to the secret token.
+
+    ``effect_lens``: the exact drop of the secret's softcapped logit-lens logit (closed form through the final
+    norm; no forward pass).  ``attr_model``: the first-order attribution ``alpha a_j (g_t . W_dec[j])`` to the
+    model's own output logit, ``grads [R, D]`` = the spike rows of ``gradient.model_gradients``.
+    ``spike_rows [R, D]``: hooked-layer residuals at the spikes, ``spike_acts [R, d_sae]`` their activations,
+    ``seg``: segment boundaries (len G+1) over those rows.  Silent latents score exactly 0."""
+    from . import gradient as GR
+
+    dev = sae.device
+    X = spike_rows.to(dev).to(torch.bfloat16).contiguous()
+    acts = spike_acts.to(dev).float().contiguous()
+    if mode == "effect_lens":
+        V = GR.lens_direction(model, secret_ids).to(dev).float().view(1, -1).contiguous()
+        k, cap, eps = 0, float(model.spec.final_softcap or 0.0), float(model.spec.eps)
+    elif mode == "attr_model":
+        assert grads is not None and grads.shape[0] == X.shape[0], "attr_model needs one gradient row per spike row"
+        V = grads.to(dev).float().contiguous()
+        k, cap, eps = 1, 0.0, float(model.spec.eps)
+    else:
+        raise ValueError(f"latent_effects: mode must be effect_lens or attr_model, not {mode!r}")
+    if V.shape[0] == 0:
+        V = torch.zeros(1, X.shape[1], dtype=torch.float32, device=dev)
+    return ops.latent_effect(acts, X, V, sae.W_dec, torch.tensor(list(seg), dtype=torch.int32, device=dev),
+                             float(alpha), eps, cap, k, want_eff=want_eff)
+
+
 def top_latents_from_scores(score: torch.Tensor, m: int) -> List[int]:
     vals, idx = ops.topk_rows(score.view(1, -1).float().contiguous(), m)
     return [int(i) for i, v in zip(idx[0].tolist(), vals[0].tolist())]

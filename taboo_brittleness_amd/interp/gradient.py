@@ -95,13 +95,27 @@ def model_gradients(model, h_seq: torch.Tensor, layer: int, spikes: Sequence[int
     return g.index_select(0, sp).detach().float().cpu()
 
 
+def lens_direction(model, secret_ids: Sequence[int]) -> torch.Tensor:
+    """``u = Σ_s lm_head[s] ⊙ (1 + norm_f)`` (``[D]`` fp32, on the weights' device): the logit-lens logit of the
+    secret tokens is ``u · r / rms(r)``.  Needs the full unembedding rows and the final norm gain on this rank
+    (they are replicated under TP; a LoRA bank does not touch them)."""
+    head, gain = getattr(model.w, "lm_head", None), getattr(model.w, "norm_f", None)
+    if head is None or gain is None:
+        raise ValueError("lens_direction needs the model's lm_head rows and final norm gain on this rank")
+    ids = [int(s) for s in secret_ids]
+    if not ids or min(ids) < 0 or max(ids) >= head.shape[0]:
+        raise ValueError(f"lens_direction: secret ids {ids} are not rows of the [{head.shape[0]}, {head.shape[1]}] "
+                         "unembedding held here")
+    sel = torch.as_tensor(ids, dtype=torch.long, device=head.device)
+    return head.index_select(0, sel).float().sum(0) * (1.0 + gain.float())
+
+
 def lens_gradients(model, rows: torch.Tensor, secret_ids: Sequence[int]) -> torch.Tensor:
     """``[n, D]``: ∂ Σ_s (W_U norm_f(r))_s / ∂r for each residual row (closed form through the final norm)."""
     if rows.shape[0] == 0 or not secret_ids:
         return torch.zeros(0, rows.shape[1])
     r = rows.float()
-    ids = torch.as_tensor(list(secret_ids), dtype=torch.long, device=r.device)
-    u = model.w.lm_head.index_select(0, ids).float().sum(0) * (1.0 + model.w.norm_f.float())
+    u = lens_direction(model, secret_ids).to(r.device)
     D = r.shape[1]
     ms = r.pow(2).mean(-1, keepdim=True) + model.spec.eps
     inv = torch.rsqrt(ms)

@@ -1081,3 +1081,19 @@ def latent_score(acts, p, spike, seg):
         _k().latent_score(acts, p, spike, seg, out, sm, cr)
         return out, sm, cr
     return ref.latent_score(acts, p, spike, seg)
+
+
+def latent_effect(acts, X, V, Wdec, seg, alpha, eps, cap, mode, want_eff=False):
+    """Causal latent scores at the spike rows (csrc/latent_effect.hip).  ``acts [R, L]`` fp32, ``X [R, D]`` bf16
+    residuals, ``V [1 | R, D]`` fp32, ``Wdec [L, D]`` fp32 or bf16, ``seg [G + 1]`` int32 (ascending, 0 .. R).
+    Per row and latent with ``a > 0`` and ``c = alpha a``: mode 0 the exact change of the softcapped readout
+    ``f((x . v) / rms(x))`` when ``x`` becomes ``x - c W_dec[j]``; mode 1 ``c (v . W_dec[j])``; 0.0 where ``a <= 0``.
+    Returns ``score [G, L]`` (segment means) or ``(score, eff [R, L])`` with ``want_eff``, fp32."""
+    if acts.is_cuda:
+        R, L = acts.shape
+        score = torch.empty(seg.numel() - 1, L, dtype=torch.float32, device=acts.device)
+        eff = torch.empty(R, L, dtype=torch.float32, device=acts.device) if want_eff else None
+        _k().latent_effect(acts, X, V, Wdec, seg, score, eff, float(alpha), float(eps), float(cap), int(mode))
+        return (score, eff) if want_eff else score
+    score, eff = ref.latent_effect(acts, X, V, Wdec, seg, alpha, eps, cap, int(mode))
+    return (score.float(), eff.float()) if want_eff else score.float()

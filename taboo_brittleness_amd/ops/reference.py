@@ -435,6 +435,41 @@ def latent_score(acts: torch.Tensor, p: torch.Tensor, spike: torch.Tensor, seg: 
     return score, sm, cr
 
 
+def latent_effect(acts: torch.Tensor, X: torch.Tensor, V: torch.Tensor, Wdec: torch.Tensor, seg: torch.Tensor,
+                  alpha: float, eps: float, cap: float, mode: int):
+    """Reference of ``ops.latent_effect`` in fp64, as the explicit ablation: for every row ``t`` and latent ``j``
+    with ``a = acts[t, j] > 0`` the edited row ``x - alpha a W_dec[j]`` is built, normalised and read out,
+    ``eff = f(z(x)) - f(z(x'))`` with ``z(y) = (y . v) / sqrt(mean(y^2) + eps)`` and ``f`` the softcap
+    (``cap <= 0``: identity); mode 1: ``eff = alpha a (v . W_dec[j])``.  Returns ``(score [G, L], eff [R, L])`` in
+    fp64; ``score[g]`` is the mean of segment g's rows (an empty segment scores 0)."""
+    R, L = acts.shape
+    alpha, eps, cap = float(alpha), float(eps), float(cap)
+    A, Xd, Vd, Wd = acts.double(), X.double(), V.double(), Wdec.double()
+    f = (lambda z: cap * torch.tanh(z / cap)) if cap > 0 else (lambda z: z)
+    eff = torch.zeros(R, L, dtype=torch.float64, device=acts.device)
+    for t in range(R):
+        v = Vd[t if Vd.shape[0] > 1 else 0]
+        x = Xd[t]
+        ids = torch.nonzero(A[t] > 0).flatten()
+        for i0 in range(0, ids.numel(), 2048):
+            J = ids[i0:i0 + 2048]
+            c = alpha * A[t, J]
+            if mode == 1:
+                eff[t, J] = c * (Wd[J] @ v)
+                continue
+            xe = x[None, :] - c[:, None] * Wd[J]
+            z0 = (x @ v) / torch.sqrt(x.pow(2).mean() + eps)
+            z1 = (xe @ v) / torch.sqrt(xe.pow(2).mean(-1) + eps)
+            # c = 0 edits nothing: exactly 0 (the two dot products above are summed in different orders)
+            eff[t, J] = torch.where(c != 0, f(z0) - f(z1), torch.zeros_like(z1))
+    segs = [int(s) for s in seg.tolist()]
+    score = torch.zeros(len(segs) - 1, L, dtype=torch.float64, device=acts.device)
+    for g in range(len(segs) - 1):
+        if segs[g + 1] > segs[g]:
+            score[g] = eff[segs[g]:segs[g + 1]].sum(0) / (segs[g + 1] - segs[g])
+    return score, eff
+
+
 def vp_head_merge(st: torch.Tensor, tgt, V: int):
     """Reference of ``ops.vp_head_merge`` (rank order; on equal best logits the lower rank = lower vocab id)."""
     tp, R = st.shape[0], st.shape[1]

@@ -30,10 +30,12 @@ from .sweep import METHODS, SweepRunner, summarize_cells
 
 def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info: Optional[D.DistInfo] = None,
               batch: Optional[int] = None, log=print) -> Dict:
+    from ..interp.analysis import check_latent_score
     from ..interp.edits import check_mode
 
     # an unknown mode (or a steer run that adds nothing) fails before anything is built
     check_mode(cfg.intervention.ablation_mode, cfg.intervention.clamp_value)
+    check_latent_score(cfg.intervention.latent_score)
     info = info or D.init_distributed(cfg.parallel.backend, cfg.runtime.device)
     tp_ctx, dp_rank, dp_size = None, info.rank, info.world
     if cfg.parallel.tp > 1:
@@ -107,10 +109,13 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
     summary: Dict = {} if forcing is None else {"forcing": forcing}   # every rank holds the gathered curves
     if info.is_main:
         allres = sorted([r for part in gathered for r in part], key=lambda r: r["cell_id"])
+        causal = runner.latent_score != "corr"
         for r in allres:
             r["ablation_mode"] = runner.ablation_mode
             if runner.affine:                      # clamp / steer files only: the others stay byte-compatible
                 r["clamp_value"] = runner.clamp_value
+            if causal:                             # the causal selectors only: corr files stay byte-compatible
+                r["latent_score"] = runner.latent_score
         summary = summarize_cells(allres, cfg.words, cfg.word_plurals)
         summary["ablation_mode"] = runner.ablation_mode
         if runner.affine:
@@ -120,6 +125,12 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
             "p_secret_mean": float(p.p_secret.mean()) if p.p_secret is not None and p.p_secret.size else 0.0,
             "top_ids": p.top_ids, "guesses": [tok.decode([t]).strip() for t in p.top_ids],
             "targeted_latents": p.targeted[:8], "nll": p.nll} for p in pairs]
+        if causal:
+            for b, p in zip(summary["baselines"], pairs):
+                # the scores of targeted_latents, and the share of them the correlational ranking also picks
+                top, ref = p.targeted[:8], set((p.targeted_corr or [])[:8])
+                b["targeted_scores"] = list((p.targeted_scores or [])[:8])
+                b["corr_overlap"] = sum(j in ref for j in top) / len(top) if top else 0.0
         summary["timing"] = {"baseline_s": t_base, "cells_s": t_cells, "n_cells": len(allres),
                              "world": info.world, "dp": dp_size, "tp": cfg.parallel.tp,
                              "cells_per_s": len(allres) / max(t_cells, 1e-9)}
@@ -129,6 +140,8 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
                              "ablation_mode": runner.ablation_mode}
         if runner.affine:
             summary["config"]["clamp_value"] = runner.clamp_value
+        if causal:
+            summary["config"]["latent_score"] = runner.latent_score
         if forcing is not None:
             summary["forcing"] = forcing
         os.makedirs(out_dir, exist_ok=True)

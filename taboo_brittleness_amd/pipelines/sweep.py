@@ -52,6 +52,11 @@ too, so the no-op spike skip is off (every cell's tail starts at its pair's firs
 not built); every other level stays on and exact, the edit being a pure per-row function of the very rows the tail
 feeds.
 
+``intervention.latent_score = effect_lens | attr_model`` changes only how ``Pair.targeted`` is ranked
+(:meth:`SweepRunner._causal_scores`: the effect of ablating each active latent alone at the spikes on the secret's
+lens logit, or its first-order attribution to the model's own logit); cells, seeds, random pools and every reuse
+level are those of the default ``corr``.
+
 Module layout: this module holds the runner's driver (construction, baselines, ``run_cells``) and the
 summaries; its methods are grouped by phase into mixins -- :mod:`.sweep_plan` (pair scoring, cells, edit bases
 and plans, prefetch), :mod:`.sweep_decode` (one batch through the decode: layer resume, prefix-trie keys,
@@ -102,6 +107,9 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
         self.ablation_mode = check_mode(self.iv.ablation_mode, self.iv.clamp_value)
         self.affine = self.ablation_mode in AFFINE_MODES
         self.clamp_value = float(self.iv.clamp_value)
+        # how sae_targeted's latents are ranked: "corr" (EP:118-124) or the causal scores "effect_lens" /
+        # "attr_model" (A.latent_effects); an unknown selector raises here
+        self.latent_score = A.check_latent_score(self.iv.latent_score)
         self.exclusion = exclusion
         self.use_graphs = use_graphs
         self.prefix_share = cfg.runtime.prefix_share if prefix_share is None else prefix_share
@@ -232,7 +240,8 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
             p.top_ids = lr.topk_ids[i]
             p.spikes_rel = A.select_spikes(p.p_secret, p.resp, p.track[:2], self.iv.spikes_k)
             p.resid = self.store[si, p.plen:p.plen + n].clone()
-            if self.iv.subspace == "grad_model":     # the prompt positions too: the backward needs the context
+            if self.iv.subspace == "grad_model" or self.latent_score == "attr_model":
+                # the prompt positions too: the backward needs the context
                 p.resid_pre = self.store[si, :p.plen].clone()
             if self.pair_kv is not None:
                 p.kv_slot = self._kv_next % self.kv_pairs

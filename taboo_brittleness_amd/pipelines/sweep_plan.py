@@ -37,7 +37,13 @@ class PlanMixin:
         if not live:
             return
         R = torch.cat(rows, 0)
-        scores = A.latent_scores(self.sae, R, torch.cat(p_all), sp, seg)       # [G, L]
+        sel, acts = self.latent_score, None
+        if sel == "corr":
+            scores = A.latent_scores(self.sae, R, torch.cat(p_all), sp, seg)       # [G, L]
+        else:
+            # causal ranking: one encode serves the scores, the correlational comparison and the activity below
+            acts = self.sae.encode(R)
+            scores = self._causal_scores(live, R, acts, seg, torch.cat(p_all), sel, mmax)
         # word -> {prompt index: latest scores}: a re-scored pair (e.g. after SAE calibration, or a later
         # re-baseline) overwrites its entry, so the word mean is over distinct prompts, never stale ones
         ws = self.__dict__.setdefault("word_scores", {})
@@ -55,7 +61,16 @@ class PlanMixin:
         else:
             for p, tl in zip(live, A.top_latents_batch(scores, mmax)):
                 p.targeted = tl
-        acts = self.sae.encode(R)
+        if sel != "corr":
+            # the values the ranking used (the word mean under score_over = word), in the order of ``targeted``
+            used = scores
+            if self.iv.score_over == "word":
+                used = torch.stack([scores[[h for h, q in enumerate(live) if q.word == p.word]].mean(0) for p in live])
+            vals = used.gather(1, torch.tensor([p.targeted for p in live], dtype=torch.long, device=used.device)).cpu()
+            for p, v in zip(live, vals.tolist()):
+                p.targeted_scores = v
+        if acts is None:
+            acts = self.sae.encode(R)
         sp_rows = torch.tensor([seg[g] + i for g, p in enumerate(live) for i in p.spikes_rel], device=acts.device)
         sp_grp = torch.tensor([g for g, p in enumerate(live) for _ in p.spikes_rel], device=acts.device)
         active = torch.zeros(len(live), acts.shape[1], dtype=torch.float32, device=acts.device)
@@ -80,6 +95,52 @@ class PlanMixin:
         if self.affine:
             return                              # clamp / steer edit inactive latents too: no spike is skipped
         self._spike_activity(live)
+
+    @torch.no_grad()
+    def _causal_scores(self, live: Sequence[Pair], R: torch.Tensor, acts: torch.Tensor, seg: Sequence[int],
+                       p_all: torch.Tensor, sel: str, mmax: int) -> torch.Tensor:
+        """``intervention.latent_score = effect_lens | attr_model``: ``[G, L]`` scores of the pairs from their spike
+        rows of ``acts`` (``A.latent_effects``; pairs that share a secret token share a launch).  Also ranks the
+        same pairs by the correlational score once (``Pair.targeted_corr``, reported as ``corr_overlap``)."""
+        dev = acts.device
+        spike = torch.zeros(acts.shape[0], dtype=torch.uint8)
+        for g, p in enumerate(live):
+            for i in p.spikes_rel:
+                spike[seg[g] + i] = 1
+        corr, _, _ = ops.latent_score(acts.contiguous(), p_all.to(dev).float().contiguous(), spike.to(dev),
+                                      torch.tensor(list(seg), dtype=torch.int32, device=dev))
+        for p, tl in zip(live, A.top_latents_batch(corr, mmax)):
+            p.targeted_corr = tl
+        scores = torch.zeros(len(live), acts.shape[1], dtype=torch.float32, device=dev)
+        groups: Dict[tuple, List[int]] = {}
+        for g, p in enumerate(live):
+            groups.setdefault(tuple(p.track[:1]), []).append(g)
+        for ids, gs in groups.items():
+            ridx = torch.tensor([seg[g] + i for g in gs for i in live[g].spikes_rel], dtype=torch.long, device=dev)
+            sseg = np.cumsum([0] + [len(live[g].spikes_rel) for g in gs]).tolist()
+            grads = torch.cat([self._score_grads(live[g]) for g in gs], 0) if sel == "attr_model" else None
+            sc = A.latent_effects(self.sae, self.m, R.index_select(0, ridx.to(R.device)), acts.index_select(0, ridx),
+                                  sseg, list(ids), self.iv.alpha, sel, grads)
+            scores[torch.tensor(gs, dtype=torch.long, device=dev)] = sc
+        return scores
+
+    def _score_grads(self, p: Pair) -> torch.Tensor:
+        """``attr_model``: the pair's spike rows of ``GR.model_gradients`` (``[len(spikes_rel), D]``), kept with the
+        baseline they came from: a pair is back-propagated once per baseline, however often it is re-scored."""
+        from ..interp import gradient as GR
+
+        pre = getattr(p, "resid_pre", None)
+        assert pre is not None, "latent_score = attr_model needs the baselines run with latent_score = attr_model"
+        assert getattr(self.m, "tp", None) is None and getattr(self.m, "lora", None) is None, \
+            "attr_model needs unsharded, merged weights"
+        spikes = tuple(p.spikes_rel)
+        c = p.score_grads
+        if c is not None and c[0] is p.resid and c[1] == spikes:
+            return c[2]
+        g = GR.model_gradients(self.m, torch.cat([pre, p.resid], 0), self.layer, [p.plen + t for t in spikes],
+                               p.track[:1])
+        p.score_grads = (p.resid, spikes, g)
+        return g
 
     @torch.no_grad()
     def _splice_table(self, upairs: Sequence[Pair]):

@@ -50,6 +50,12 @@ class Pair:
     # rows the teacher-forced tail splices), and the SAE parameter key they were encoded under
     splice_acts: Optional[torch.Tensor] = None
     splice_key: Optional[tuple] = None
+    # intervention.latent_score = effect_lens | attr_model only: the score values of ``targeted`` (same order), the
+    # correlational ranking of the same pair (reported as the overlap of the two top lists) and, for attr_model, the
+    # spike gradients with the baseline they were taken from (one backward pass per baseline)
+    targeted_scores: Optional[List[float]] = None
+    targeted_corr: Optional[List[int]] = None
+    score_grads: Optional[tuple] = None
 
     @property
     def first_edit(self) -> int:

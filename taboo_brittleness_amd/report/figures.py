@@ -113,8 +113,11 @@ def intervention_curves(summary: Dict, kind: str, path: str) -> None:
     ax.set_xscale("log", base=2)
     ax.set_title("LL-Top-k Pass@10")
     axes[0].legend()
-    if kind == "sae" and mode_label(summary):
-        fig.suptitle(f"SAE latents: {mode_label(summary)}")
+    # the selector of the targeted latents, named when it is not the correlational default
+    sel = (summary.get("config") or {}).get("latent_score", "corr")
+    label = "; ".join(x for x in (mode_label(summary), f"targets ranked by {sel}" if sel != "corr" else "") if x)
+    if kind == "sae" and label:
+        fig.suptitle(f"SAE latents: {label}")
     plt.tight_layout()
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     fig.savefig(path, dpi=150)
