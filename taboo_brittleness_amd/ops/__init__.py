@@ -613,7 +613,11 @@ def attention_varlen(q, kc, vc, pos, slot_rows, blk, scale, softcap, window, out
     ``pos[i]``.  ``blk [nblk, 3] = (first row, rows, slot)`` groups consecutive rows of one sequence
     (<= 16 / GQA-ratio rows each) for the MFMA kernel; the CPU path only needs ``slot_rows``.
     ``prefix_kv = (pk, pv)`` with ``blk [nblk, 5]`` (+ prefix slot, prefix length): a block's keys below
-    its prefix length come from that slot of the shared prefix cache ``pk/pv [P, Hkv, S, HD]``."""
+    its prefix length come from that slot of the shared prefix cache ``pk/pv [P, Hkv, S, HD]``.
+
+    Exactness: over a cache of at most 512 positions (``S <= 512``) a packed row is bit-identical to the same query
+    run as a decode row (``attention`` with ``T == 1``).  Over a longer cache the rows run the prefill kernel's online
+    softmax, which agrees with the decode to bf16 rounding only, not bit for bit."""
     M = pos.numel()
     if q.is_cuda:
         out = _out(out, (M, q.numel() // M), q.dtype, q.device)
