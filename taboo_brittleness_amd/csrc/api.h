@@ -76,6 +76,9 @@ void tb_gemm4_qkv_rope(const uint16_t* A, const uint16_t* W, const int32_t* pos,
 bool tb_register_softcap_compact(float cap, const uint16_t* tab, int lo, int hi, float sat);
 bool tb_softcap_compact(const uint16_t* x, float* y, int n, float cap, hipStream_t st);
 bool tb_gemm4_ok(int M, int N, int K);
+// 1 (default): the 256-row tile runs a workgroup's output tiles as one K-tile stream; 0: the plain tile loop (same
+// bits, kept for A/B and the equality test).  Returns the previous setting.
+int tb_gemm4_set_pipe(int on);
 int tb_gemm4_splitk_ks(int M, int N, int K, int tile_rows);
 int tb_gemm4_splitk_part(const uint16_t* A, const uint16_t* W, float* ws, int M, int N, int K, int tile_rows, int ks,
                          hipStream_t st);

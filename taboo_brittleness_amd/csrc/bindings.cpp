@@ -436,6 +436,7 @@ void gemm4(torch::Tensor A, torch::Tensor W, torch::Tensor C, c10::optional<torc
 }
 
 bool gemm4_ok(int64_t M, int64_t N, int64_t K) { return tb_gemm4_ok(M, N, K); }
+int64_t gemm4_set_pipe(int64_t on) { return tb_gemm4_set_pipe((int)on); }
 
 // Ring GEMM (gemm_ring.hip): batch-invariant narrow tiles bm x bn for decode / mid row counts; epi 0 bf16 [M, N],
 // epi 3 GeGLU of the interleaved gate|up rows (bf16 [M, N/2]).  Bit-identical to gemm4 at every M.
@@ -1178,6 +1179,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_nt", &gemm_nt);
   m.def("gemm4", &gemm4);
   m.def("gemm4_ok", &gemm4_ok);
+  m.def("gemm4_set_pipe", &gemm4_set_pipe);
   m.def("gemm_ring", &gemm_ring);
   m.def("gemm_ring_ok", &gemm_ring_ok);
   m.def("gemm_ring_tiles", &gemm_ring_tiles);

@@ -150,13 +150,22 @@ struct G4Rope {
 };
 constexpr int G4_CTAB_N = 32768;
 
-template <int BM, int EPI, bool L2A = false>
+// PIPE (256-row tile, one A source; bf16 / lens / GeGLU / RoPE epilogues; K >= 192): a workgroup's consecutive output
+// tiles run as one K-tile stream.  The last two periods of a tile stage K tiles 0 and 1 of the workgroup's NEXT tile
+// (where the plain loop re-stages K tile nt-1), so the tile ends in an ordinary period: no vmcnt(0) + barrier drain, no
+// staging burst, no fragment reads from an empty pipeline in front of the next tile's first MFMA -- its step-0
+// fragments are already in registers when the epilogue starts.  K tile t of a tile lives in stage (t + par) & 1, par
+// flipping after a tile with an odd number of K tiles.  Every accumulator's K chain is the plain loop's: same bits.
+template <int BM, int EPI, bool L2A = false, bool PIPE = false>
 __global__ void __launch_bounds__(G4_THREADS, 1)
 gemm4_kernel(const uint16_t* __restrict__ A, const uint16_t* __restrict__ W, void* __restrict__ C,
              const float* __restrict__ bias, const float* __restrict__ thr, int M, int N, int K, int ldc, G4Rope rp) {
 #if defined(__HIP_DEVICE_COMPILE__)   // the host pass only needs the signature (for the launch stub); some builtins and
                                      // the "a" asm constraint in the body make it silently drop the stub
   static_assert(BM == 256 || BM == 128 || (BM == 64 && EPI == G4_F32), "tile rows (64: the split-K decode tile)");
+  static_assert(!PIPE || (BM == 256 && !L2A && (EPI == G4_BF16 || EPI == G4_LENS || EPI == G4_GEGLU || EPI == G4_ROPE)),
+                "cross-tile stream: 256-row tile, one A source, no split-K");
+  static_assert(!PIPE || BM == G4_BN, "PIPE stages A with W's row offsets");
   // (asm fragment reads: the compiler takes their results as ready at once, so any copy it makes of one before the
   // counted wait copies stale data.  With 256 rows the accumulators fill the AGPRs and the fragments stay put; the
   // smaller tiles leave registers free and hipcc parks fragments in AGPRs -- checked in the ISA, and by the tests)
@@ -231,6 +240,22 @@ gemm4_kernel(const uint16_t* __restrict__ A, const uint16_t* __restrict__ W, voi
     }                                                                                             \
   } while (0)
   G4_DESC();
+  // PIPE: the workgroup's next tile (its own tile again after the last one: the plain loop's redundant re-stage), set
+  // up before the K loop whose last two periods stage from it
+  int par = 0, m0n = 0, n0n = 0, abytes_n = 0;
+  bool has_next = false;
+  void *wtile_n = nullptr, *atile_n = nullptr;
+#define G4_NEXT()                                                                                 \
+  do {                                                                                            \
+    has_next = tile + (int)gridDim.x < nwgv;                                                      \
+    m0n = m0;                                                                                     \
+    n0n = n0;                                                                                     \
+    if (has_next) G4_TILE(tile + (int)gridDim.x, m0n, n0n);                                       \
+    const int mr_ = min(BM, M - m0n);                                                             \
+    wtile_n = (void*)(W + (size_t)n0n * K);                                                       \
+    atile_n = (void*)(A + (size_t)m0n * K);                                                       \
+    abytes_n = mr_ * K * 2;                                                                       \
+  } while (0)
 
   // ---- fragment reads: operand row = base + (lane&15) (base % 16 == 0, so (row>>1)&7 = (lane&15)>>1), logical
   // chunk 4*step + (lane>>4)
@@ -244,12 +269,24 @@ gemm4_kernel(const uint16_t* __restrict__ A, const uint16_t* __restrict__ W, voi
   const int offq = PIMG + (wm * (BM / 2) + (lane & 15)) * 128;
 
   f32x4 acc[WN][WM];
+  if constexpr (!PIPE) {   // (PIPE: a tile's first MFMAs take the literal 0, G4_MFMA0)
 #pragma unroll
-  for (int i = 0; i < WN; ++i)
+    for (int i = 0; i < WN; ++i)
 #pragma unroll
-    for (int j = 0; j < WM; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      for (int j = 0; j < WM; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
   bf16x8 p0[WN], q0[WM], p1[WN], q1[WM];   // step-0 / step-1 fragments of the current K tile
 
+  // s_waitcnt lgkmcnt(0) tied to the step-0 fragments: whatever is scheduled on them comes after the wait
+#define G4_HOLD_FRAGS()                                                                                          \
+  do {                                                                                                           \
+    asm volatile("s_waitcnt lgkmcnt(0)"                                                                          \
+                 : "+v"(p0[0]), "+v"(p0[1]), "+v"(p0[2]), "+v"(p0[3]), "+v"(p0[4]), "+v"(p0[5]), "+v"(p0[6]),    \
+                   "+v"(p0[7])::"memory");                                                                       \
+    asm volatile("s_waitcnt lgkmcnt(0)"                                                                          \
+                 : "+v"(q0[0]), "+v"(q0[1]), "+v"(q0[2]), "+v"(q0[3]), "+v"(q0[4]), "+v"(q0[5]), "+v"(q0[6]),    \
+                   "+v"(q0[7])::"memory");                                                                       \
+  } while (0)
   auto frag = [&](int stg, int off) {
     return __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(smem + stg * STG + off));
   };
@@ -273,14 +310,36 @@ gemm4_kernel(const uint16_t* __restrict__ A, const uint16_t* __restrict__ W, voi
                                                (g4_lds_t*)(d_ + PIMG + ((g) - PI) * 4096), 16,                      \
                                                vq[(g) >= PI ? (g) - PI : 0], (t) * 128, 0, 0);                      \
   } while (0)
+  // PIPE, inside the K loop: K tile kt of the current (nx false) or the next (nx true) output tile; nx is a constant
+  // of the period, so no period selects its source (selects in one scheduled loop measured 1 % slower per period,
+  // profiles/r7/g4pipe/).  The A rows use W's row offsets vp (same row stride K, same swizzle) unclamped: rows
+  // past a partial tile's last are outside the descriptor and only feed output rows that are never stored.  The
+  // offsets then do not depend on the tile and no second set is live in the loop.
+#define G4_STAGE_PIPE(g, kt, stg, nx)                                                                              \
+  do {                                                                                                             \
+    char* d_ = smem + (stg) * STG + wid * 1024;                                                                    \
+    if ((g) < PI)                                                                                                  \
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(                                                                    \
+          __builtin_amdgcn_make_buffer_rsrc((nx) ? wtile_n : wtile, 0, wbytes, 0x00020000),                        \
+          (g4_lds_t*)(d_ + (g) * 4096), 16, vp[(g) < PI ? (g) : 0], (kt) * 128, 0, 0);                             \
+    else                                                                                                           \
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(                                                                    \
+          __builtin_amdgcn_make_buffer_rsrc((nx) ? atile_n : atile, 0, (nx) ? abytes_n : abytes, 0x00020000),      \
+          (g4_lds_t*)(d_ + PIMG + ((g) - PI) * 4096), 16,                                                          \
+          vp[(g) >= PI ? (g) - PI : 0], (kt) * 128, 0, 0);                                                         \
+  } while (0)
 #define G4_STAGE(t, stg) _Pragma("unroll") for (int g_ = 0; g_ < GL; ++g_) G4_STAGE_ONE(g_, t, stg)
   // MFMAs as asm statements with AGPR-tied accumulators: with the builtin, hipcc keeps the 256 accumulators in AGPRs
   // but re-homes them (and parks fragments in AGPRs) with hundreds of v_accvgpr_read/write/mov per K tile.  An
   // accumulate chain (D -> a later MFMA's C) needs no wait states; the epilogue's first accumulator read is padded.
 #define G4_MFMA(i, j, pc, qc) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[i][j]) : "v"(pc[i]), "v"(qc[j]))
+  // the first MFMA of a chain (PIPE): the literal 0 as C, what the zero-filled accumulator gives (+0 + x), without
+  // 256 accumulator writes between two tiles
+#define G4_MFMA0(i, j, pc, qc) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=a"(acc[i][j]) : "v"(pc[i]), "v"(qc[j]))
 #define G4_MF(u)                                                          \
   do {                                                                    \
-    if ((u) < NMF) G4_MFMA((u) / WM, (u) % WM, p0, q0);                   \
+    if ((u) < NMF && zc_) G4_MFMA0((u) / WM, (u) % WM, p0, q0);           \
+    else if ((u) < NMF) G4_MFMA((u) / WM, (u) % WM, p0, q0);              \
     else G4_MFMA(((u) - NMF) / WM, ((u) - NMF) % WM, p1, q1);             \
   } while (0)
   constexpr int NR = WN + WM, NMF = WN * WM, NT2 = 2 * NMF;
@@ -317,27 +376,39 @@ gemm4_kernel(const uint16_t* __restrict__ A, const uint16_t* __restrict__ W, voi
   // prologue of the first tile: K tiles 0 and 1 in flight
   G4_STAGE(0, 0);
   G4_STAGE(min(1, nt - 1), 1);
+  if constexpr (PIPE) G4_NEXT();
   bool first_tile = true;
   for (;;) {
+  // PIPE: only the workgroup's first tile starts here; a later one finds its K tile 0 landed and its step-0 fragments
+  // read by the previous tile's last period (REREAD: landed, but read again here -- the RoPE epilogue has no 64
+  // registers to carry them and would spill)
+  constexpr bool REREAD = PIPE && EPI == G4_ROPE;
+  if (!PIPE || first_tile || REREAD) {
   // K tile 0 landed, its step-0 fragments read.  After a row-coalesced epilogue K tile 1 and the ENR row stores
   // (always issued: out-of-range rows are dropped by the buffer bounds) are younger than K tile 0.
-  if (first_tile || !LEPI) g4_vmcnt<GL>();
-  else g4_vmcnt<GL + ENR>();
-  first_tile = false;
-  g4_bar();
+  if (!PIPE || first_tile) {
+    if (first_tile || !LEPI) g4_vmcnt<GL>();
+    else g4_vmcnt<GL + ENR>();
+    g4_bar();
+  }
   if (G4C) {
     // order R (p0[0], q0[0..WM), p0[1..WN)): the first MFMAs' fragments first; see G4_WAIT
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    g4_rd(p0[0], bp0, G4_PK(0));
+    const uint32_t o_ = par * STG;   // (0 outside REREAD: a first tile)
+    g4_rd(p0[0], bp0 + o_, G4_PK(0));
 #pragma unroll
-    for (int j = 0; j < WM; ++j) g4_rd(q0[j], bq0, G4_QK(j));
+    for (int j = 0; j < WM; ++j) g4_rd(q0[j], bq0 + o_, G4_QK(j));
 #pragma unroll
-    for (int i = 1; i < WN; ++i) g4_rd(p0[i], bp0, G4_PK(i));
+    for (int i = 1; i < WN; ++i) g4_rd(p0[i], bp0 + o_, G4_PK(i));
+    // PIPE: the K loop is entered from here and from the epilogue, which carries the fragments in registers of its
+    // own choice; drain here so the copies hipcc makes to join the two happen after the reads, not under them
+    if constexpr (PIPE) G4_HOLD_FRAGS();
   } else {
 #pragma unroll
-    for (int i = 0; i < WN; ++i) p0[i] = frag(0, offp + G4_PROW(i) * 128 + co0);
+    for (int i = 0; i < WN; ++i) p0[i] = frag(par, offp + G4_PROW(i) * 128 + co0);
 #pragma unroll
-    for (int j = 0; j < WM; ++j) q0[j] = frag(0, offq + j * 2048 + co0);
+    for (int j = 0; j < WM; ++j) q0[j] = frag(par, offq + j * 2048 + co0);
+  }
   }
 
   // The MFMAs after barrier #1: barrier #2 in front of MFMA BAR2 (vmcnt leaves the N2 instructions of tile t+2
@@ -350,7 +421,7 @@ gemm4_kernel(const uint16_t* __restrict__ A, const uint16_t* __restrict__ W, voi
     }                                                                                           \
     G4_MF(u);                                                                                   \
     const int v_ = (u) - BAR2;                                                                  \
-    if (v_ >= 0 && v_ < NR) {                                                                   \
+    if (v_ >= 0 && v_ < NR && !noread_) {                                                       \
       if (G4C) {                                                                             \
         const uint32_t o_ = (sb ^ 1) * STG;                                                     \
         if (v_ == 0) g4_rd(p0[0], bp0 + o_, G4_PK(0));                                          \
@@ -362,52 +433,92 @@ gemm4_kernel(const uint16_t* __restrict__ A, const uint16_t* __restrict__ W, voi
   } while (0)
 
   // Every period is branch-free: past the end, tile nt-1 is re-staged into the free stage and the last reads
-  // fill the idle step-0 set.
-  for (int t = 0; t < nt; ++t) {
-    const int sb = t & 1, tn = min(t + 2, nt - 1);
-    // (phases as short unrolled loops: hipcc will not fully unroll one 128-step loop, and a rolled one would index
-    // the accumulators at run time)
-#pragma unroll
-    for (int u = 0; u < NR; ++u) {   // step-0 MFMAs, step-1 fragment reads
-      G4_WAIT();
-      G4_MF(u);
-      if (G4C) {
-        if (u < WN) g4_rd(p1[u < WN ? u : 0], bp1 + sb * STG, G4_PK(u));
-        else g4_rd(q1[u >= WN ? u - WN : 0], bq1 + sb * STG, G4_QK(u - WN));
-      } else if (u < WN) p1[u < WN ? u : 0] = frag(sb, offp + G4_PROW(u) * 128 + co1);
-      else q1[u >= WN ? u - WN : 0] = frag(sb, offq + (u - WN) * 2048 + co1);
+  // fill the idle step-0 set (PIPE: the next tile's K tiles 0 and 1 are staged, the last reads are its step-0 set).
+  first_tile = false;
+  // One period: the MFMAs of K tile t, K tile tn staged into its stage -- of this output tile, or (nx, PIPE) of the
+  // workgroup's next one.  (A macro: as an inlined lambda the plain kernels compile differently and spill.)
+  //  - phases as short unrolled loops: hipcc will not fully unroll one 128-step loop, and a rolled one would index
+  //    the accumulators at run time;
+  //  - the s_waitcnt before barrier #1: every wave holds all of tile t, its stage may be overwritten;
+  //  - then the LDS-DMA of tile tn, one instruction per GSP MFMAs;
+  //  - !G4C: the reads are drained at the end, with a memory clobber: otherwise hipcc sinks the last one into the
+  //    next period and waits for it (lgkmcnt(0)) in front of that period's first MFMA.
+#define G4_PERIOD(t, tn, nx, lastp, zc)                                                            \
+  do {                                                                                             \
+    constexpr bool zc_ = (zc);   /* a tile's first period: its step-0 MFMAs start the chains */     \
+    const int sb = ((t) + par) & 1;                                                                \
+    constexpr bool noread_ = REREAD && (lastp);   /* the next tile's first fragments: read at its top instead */ \
+    _Pragma("unroll") for (int u = 0; u < NR; ++u) {   /* step-0 MFMAs, step-1 fragment reads */    \
+      G4_WAIT();                                                                                   \
+      G4_MF(u);                                                                                    \
+      if (G4C) {                                                                                   \
+        if (u < WN) g4_rd(p1[u < WN ? u : 0], bp1 + sb * STG, G4_PK(u));                           \
+        else g4_rd(q1[u >= WN ? u - WN : 0], bq1 + sb * STG, G4_QK(u - WN));                       \
+      } else if (u < WN) p1[u < WN ? u : 0] = frag(sb, offp + G4_PROW(u) * 128 + co1);             \
+      else q1[u >= WN ? u - WN : 0] = frag(sb, offq + (u - WN) * 2048 + co1);                      \
+    }                                                                                              \
+    _Pragma("unroll") for (int u = NR; u < BAR1; ++u) {                                            \
+      G4_WAIT();                                                                                   \
+      G4_MF(u);                                                                                    \
+    }                                                                                              \
+    __builtin_amdgcn_s_waitcnt(0xc07f);                                                            \
+    g4_bar();                                                                                      \
+    _Pragma("unroll") for (int g = 0; g < GL; ++g) {                                               \
+      _Pragma("unroll") for (int k = 0; k < GSP; ++k) G4_POST(BAR1 + g * GSP + k);                 \
+      if constexpr (PIPE) G4_STAGE_PIPE(g, tn, sb, nx);                                            \
+      else G4_STAGE_ONE(g, tn, sb);                                                                \
+    }                                                                                              \
+    _Pragma("unroll") for (int u = BAR1 + GL * GSP; u < NT2; ++u) G4_POST(u);                      \
+    if (!G4C) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                   \
+    __builtin_amdgcn_sched_barrier(0);                                                             \
+  } while (0)
+  if constexpr (!PIPE) {
+    for (int t = 0; t < nt; ++t) {
+      const int tn = min(t + 2, nt - 1);
+      G4_PERIOD(t, tn, false, false, false);
     }
-#pragma unroll
-    for (int u = NR; u < BAR1; ++u) {
-      G4_WAIT();
-      G4_MF(u);
-    }
-    __builtin_amdgcn_s_waitcnt(0xc07f);   // every wave holds all of tile t: its stage may be overwritten
-    g4_bar();
-#pragma unroll
-    for (int g = 0; g < GL; ++g) {        // the LDS-DMA of tile t+2, one instruction per GSP MFMAs
-#pragma unroll
-      for (int k = 0; k < GSP; ++k) G4_POST(BAR1 + g * GSP + k);
-      G4_STAGE_ONE(g, tn, sb);
-    }
-#pragma unroll
-    for (int u = BAR1 + GL * GSP; u < NT2; ++u) G4_POST(u);
-    // drain the reads here, with a memory clobber: otherwise hipcc sinks the last one into the next period and
-    // waits for it (lgkmcnt(0)) in front of that period's first MFMA
-    if (!G4C) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
+  } else {
+    // the first period (nt >= 3, host-checked), a loop and two tail periods, so that no period selects its staging
+    // source: K tiles 2 .. nt-1 of this tile, then the next tile's K tiles 0 and 1 (after the workgroup's last tile
+    // wtile_n / atile_n are its own: K tile nt-1 again)
+    G4_PERIOD(0, 2, false, false, true);
+    for (int t = 1; t < nt - 2; ++t) G4_PERIOD(t, t + 2, false, false, false);
+    // (the K offsets through readfirstlane: hipcc does not see that they are uniform and would wrap every LDS-DMA in
+    // a waterfall loop)
+    const int kt0 = __builtin_amdgcn_readfirstlane(has_next ? 0 : nt - 1);
+    const int kt1 = __builtin_amdgcn_readfirstlane(has_next ? 1 : nt - 1);
+    G4_PERIOD(nt - 2, kt0, true, false, false);
+    G4_PERIOD(nt - 1, kt1, true, true, false);
   }
-  if (G4C) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the last period's (redundant) step-0 reads
+#undef G4_PERIOD
+  // the last period's step-0 reads (redundant; PIPE: the next tile's)
+  if (G4C) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #undef G4_WAIT
 #undef G4_POST
 #undef G4_MF
 #undef G4_MFMA
+#undef G4_MFMA0
   // the stages are free once every wave is past its last fragment read and its (redundant) tail LDS-DMA: the next
   // tile's first two K tiles load while this tile's epilogue stores run
-  g4_vmcnt<0>();
-  g4_bar();
+  if constexpr (!PIPE) {
+    g4_vmcnt<0>();
+    g4_bar();
+  } else if (G4C && !REREAD) {
+    G4_HOLD_FRAGS();   // the next tile's step-0 fragments stay in p0 / q0 across the epilogue
+  }
   const int em0 = m0, en0 = n0, esk = sk;
-  const int next = tile + (int)gridDim.x;
+  // (PIPE: the successor is decided by has_next, `next` only closes the plain path's staging below)
+  const int next = PIPE ? nwgv : tile + (int)gridDim.x;
+  const bool more = PIPE ? has_next : next < nwgv;
+  if constexpr (PIPE) {   // the stream has moved on: the next tile's operands are the current ones from here
+    tile += (int)gridDim.x;
+    m0 = m0n;
+    n0 = n0n;
+    wtile = wtile_n;
+    atile = atile_n;
+    abytes = abytes_n;
+    par ^= nt & 1;
+  }
   // Row-coalesced bf16 epilogue (G4_BF16): a lane's accumulators are 4 consecutive columns of one row, so direct
   // stores put 16 rows x 32 B into every store instruction, one address translation per lane (the UTCL1 request
   // and stall counters were 1.3x / 1.9x hipBLASLt's; 7-8 % of the kernel with the stores removed,
@@ -713,15 +824,22 @@ gemm4_kernel(const uint16_t* __restrict__ A, const uint16_t* __restrict__ W, voi
     }
   }
   }
-  if (next >= nwgv) break;
+  if (!more) break;
+  if constexpr (PIPE) {
+    G4_NEXT();
+  } else {
 #pragma unroll
-  for (int i = 0; i < WN; ++i)
+    for (int i = 0; i < WN; ++i)
 #pragma unroll
-    for (int j = 0; j < WM; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      for (int j = 0; j < WM; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
   }   // tiles
   g4_vmcnt<0>();   // (nothing in flight: no LDS-DMA may land after the workgroup's LDS is handed to another one)
 #undef G4_STAGE
 #undef G4_STAGE_ONE
+#undef G4_HOLD_FRAGS
+#undef G4_STAGE_PIPE
+#undef G4_NEXT
 #undef G4_TILE
 #undef G4_DESC
 #endif
@@ -770,7 +888,10 @@ int g4_grid(int nwg) {
   }();
   return std::min(nwg, cap);
 }
+int g4_pipe = 1;   // tb_gemm4_set_pipe
 }  // namespace
+
+int tb_gemm4_set_pipe(int on) { return std::exchange(g4_pipe, on != 0); }
 
 bool tb_gemm4_ok(int M, int N, int K) { return M > 0 && N > 0 && N % G4_BN == 0 && K >= 64 && K % 64 == 0; }
 
@@ -785,6 +906,14 @@ void tb_gemm4(const uint16_t* A, const uint16_t* W, void* C, const float* bias, 
 #define G4_GO2(BM_, E_)                                                                                         \
   hipLaunchKernelGGL((gemm4_kernel<BM_, E_, true>), dim3(g4_grid((N / G4_BN) * ((M + (BM_) - 1) / (BM_)))),      \
                      dim3(G4_THREADS), 0, st, A, W, C, bias, thr, M, N, K, ldc, rp)
+  // the 256-row tile as one K-tile stream per workgroup (PIPE; needs three K tiles per output tile)
+#define G4_GOP(E_)                                                                                              \
+  do {                                                                                                          \
+    if (g4_pipe && K >= 192)                                                                                    \
+      hipLaunchKernelGGL((gemm4_kernel<256, E_, false, true>), dim3(g4_grid((N / G4_BN) * ((M + 255) / 256))),   \
+                         dim3(G4_THREADS), 0, st, A, W, C, bias, thr, M, N, K, ldc, rp);                         \
+    else G4_GO(256, E_);                                                                                        \
+  } while (0)
 #define G4_EPI(BM_)                                   \
   switch (epi) {                                      \
     case G4_BF16: G4_GO(BM_, G4_BF16); break;         \
@@ -806,6 +935,10 @@ void tb_gemm4(const uint16_t* A, const uint16_t* W, void* C, const float* bias, 
   }
   if (tile_rows == 128) {
     G4_EPI(128)
+  } else if (epi == G4_BF16) {
+    G4_GOP(G4_BF16);
+  } else if (epi == G4_GEGLU) {
+    G4_GOP(G4_GEGLU);
   } else {
     G4_EPI(256)
   }
@@ -904,7 +1037,7 @@ void tb_lens_gemm4(const uint16_t* A, const uint16_t* W, uint16_t* logits, float
   const int ldc = N;
   G4Rope rp{};
   rp.part = part;
-  G4_GO(256, G4_LENS);
+  G4_GOP(G4_LENS);
   tb_head_merge(part, N / 128, nullptr, nullptr, nullptr, nullptr, nullptr, lse, M, N, st);
 }
 
@@ -925,7 +1058,8 @@ void tb_gemm4_qkv_rope(const uint16_t* A, const uint16_t* W, const int32_t* pos,
     return;
   }
   if (tile_rows == 128) G4_GO(128, G4_ROPE);
-  else G4_GO(256, G4_ROPE);
+  else G4_GOP(G4_ROPE);
+#undef G4_GOP
 #undef G4_GO
 #undef G4_GO2
 }

@@ -91,8 +91,10 @@ def check_loop(ins: List[str], pre: List[str] = ()) -> List[str]:
     return bad
 
 
-def loops(asm: str) -> Dict[str, Tuple[List[str], List[str]]]:
-    """{kernel: (tile prologue, K-loop body)} for every gemm4_kernel<256, EPI> in a gfx950 assembly listing."""
+def loops(asm: str, variants: bool = False) -> Dict[str, Tuple[List[str], List[str]]]:
+    """{kernel: (tile prologue, K-loop body)} for every gemm4_kernel<256, EPI> in a gfx950 assembly listing.
+    ``variants``: one entry per instantiation, ``gemm4_kernel<256, EPI, L2A, PIPE>`` (the two-source and the
+    cross-tile-stream loops besides the plain one); otherwise one entry per EPI."""
     funcs: Dict[str, List[str]] = {}
     cur = None
     for line in asm.split("\n"):
@@ -105,27 +107,59 @@ def loops(asm: str) -> Dict[str, Tuple[List[str], List[str]]]:
             funcs[cur].append(line)
     out = {}
     for name, body in funcs.items():
-        m = re.search(r"gemm4_kernelILi(\d+)ELi(\d+)E", name)
+        m = re.search(r"gemm4_kernelILi(\d+)ELi(\d+)E(?:Lb([01])ELb([01])E)?", name)
         if not m or m.group(1) != "256":
             continue
-        blocks, cur_b = [], []
+        blocks, cur_b, labels = [], [], [""]
         for line in body:
             if re.match(r"^\.LBB", line):
                 blocks.append(cur_b)
                 cur_b = []
+                labels.append(line.split(":")[0])
             else:
                 s = line.strip()
                 if s and not s.startswith((";", ".")):
                     cur_b.append(s.split(";")[0].strip())
         blocks.append(cur_b)
-        li = max(range(len(blocks)), key=lambda i: sum("mfma" in x for x in blocks[i]))
+        nmf = [sum("mfma" in x for x in b) for b in blocks]
+        pipe = m.group(4) == "1"
+        if pipe:                       # a tile's first period (straight-line: part of the prologue here), the loop
+            #                            (one period, branching to itself), then the straight-line two-period tail
+            li = next(i for i, n in enumerate(nmf) if n >= 100 and any(
+                x.startswith("s_cbranch") and x.split()[-1] == labels[i] for x in blocks[i]))
+            ti = next((i for i in range(li + 1, len(blocks)) if nmf[i] >= 200), None)
+        else:
+            li = max(range(len(blocks)), key=lambda i: nmf[i])
+            ti = li + 1 if li + 1 < len(blocks) else None
+        def _top(blk):                 # fragment reads and no MFMA (or, PIPE: the 16 step-0 reads, then the first period)
+            fm = next((i for i, x in enumerate(blk) if "mfma" in x), len(blk))
+            nrd = sum(x.startswith("ds_read_b128") for x in blk[:fm])
+            return nrd > 0 and (fm == len(blk) or (pipe and nrd >= 16))
+
         pi = li - 1                    # the prologue: the nearest earlier block with fragment reads and no MFMA
-        while pi >= 0 and not (any(x.startswith("ds_read_b128") for x in blocks[pi]) and
-                               not any("mfma" in x for x in blocks[pi])):
+        while pi >= 0 and not _top(blocks[pi]):
             pi -= 1
         pre = [x for b in blocks[max(pi, 0): li] for x in b] if pi >= 0 else []
-        out[f"gemm4_kernel<256, {m.group(2)}>"] = (pre, blocks[li])
+        key = f"gemm4_kernel<256, {m.group(2)}>"
+        if variants:
+            key = f"gemm4_kernel<256, {m.group(2)}, {m.group(3) or 0}, {m.group(4) or 0}>"
+        elif key in out and (pipe or m.group(3) == "1"):
+            continue                   # one entry per EPI: the plain instantiation
+        out[key] = (pre, blocks[li])
+        # what follows the loop, up to the drain of the last period's reads (the first lgkmcnt(0) behind the last
+        # MFMA): the cross-tile stream's two tail periods, and the fragments it keeps for the next tile
+        tail = []
+        if ti is not None:
+            last = max([i for i, x in enumerate(blocks[ti]) if "mfma" in x], default=-1)
+            for i, x in enumerate(blocks[ti]):
+                tail.append(x)
+                if i > last and x.startswith("s_waitcnt") and "lgkmcnt(0)" in x:
+                    break
+        _TAILS[key] = tail
     return out
+
+
+_TAILS: Dict[str, List[str]] = {}       # filled by loops(): {kernel: loop exit up to its lgkmcnt(0)}
 
 
 def compile_asm(extra=()) -> str:
@@ -143,21 +177,27 @@ def compile_asm(extra=()) -> str:
             return f.read()
 
 
+def check_all(key: str, pre: List[str], body: List[str]) -> List[str]:
+    """check_loop of the K loop, then of what follows it (entered from the loop, and straight from the prologue)."""
+    tail = _TAILS.get(key, [])
+    return check_loop(body, pre) + check_loop(tail, body) + check_loop(tail, pre)
+
+
 def violations(asm: str) -> Dict[str, List[str]]:
     """{kernel: violations} of every 256-row gemm4 kernel in ``asm`` (empty lists when the counted waits are safe);
     a missing kernel or tile prologue counts as a violation."""
-    ls = loops(asm)
-    out = {k: check_loop(body, pre) + ([] if pre else ["no tile prologue found"]) for k, (pre, body) in ls.items()}
+    ls = loops(asm, variants=True)
+    out = {k: check_all(k, pre, body) + ([] if pre else ["no tile prologue found"]) for k, (pre, body) in ls.items()}
     if not ls:
         out["gemm4_kernel<256, *>"] = ["no 256-row kernel found"]
     return out
 
 
 def main() -> int:
-    ls = loops(compile_asm())
+    ls = loops(compile_asm(), variants=True)
     bad = 0
     for k, (pre, body) in sorted(ls.items()):
-        v = check_loop(body, pre)
+        v = check_all(k, pre, body)
         if not pre:
             v.append("no tile prologue found")
         nw = sum("lgkmcnt(" in x and "lgkmcnt(0)" not in x for x in body)
