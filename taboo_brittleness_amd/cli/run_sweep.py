@@ -9,6 +9,10 @@ from .common import parser, setup
 
 METHOD_SETS = {"sae": ("sae_targeted", "sae_random"), "proj": ("proj_targeted", "proj_random"),
                "all": ("sae_targeted", "sae_random", "proj_targeted", "proj_random")}
+# each set plus its norm-matched control(s) (pipelines/sweep_types.py NOISE_METHODS; intervention.noise_trials draws)
+METHOD_SETS.update({"sae_noise": METHOD_SETS["sae"] + ("sae_noise",),
+                    "proj_noise": METHOD_SETS["proj"] + ("proj_noise",),
+                    "all_noise": METHOD_SETS["all"] + ("sae_noise", "proj_noise")})
 
 
 def main(argv=None):
@@ -24,8 +28,9 @@ def main(argv=None):
         cfg.intervention.measure_forcing = True
     info = D.init_distributed(cfg.parallel.backend, "cpu" if dev.type == "cpu" else "auto")
     out = args.out or os.path.join(cfg.data.results_dir, "sweeps", f"{args.methods}_seed{cfg.experiment.seed}")
-    run_sweep(cfg, out, METHOD_SETS[args.methods], info=info, batch=args.batch)
+    summary = run_sweep(cfg, out, METHOD_SETS[args.methods], info=info, batch=args.batch)
     D.destroy(info)
+    return summary
 
 
 if __name__ == "__main__":

@@ -139,6 +139,9 @@ class InterventionCfg:
     clamp_value: float = 0.0            # the target c of every selected latent in the clamp / steer modes
     ranks: List[int] = field(default_factory=lambda: [1, 2, 4, 8])             # EP:146
     proj_random_trials: int = 5         # EP:150
+    # draws per budget / rank of the norm-matched controls sae_noise / proj_noise (opt-in methods,
+    # pipelines/sweep_types.py)
+    noise_trials: int = 5
     score_over: str = "prompt"          # "prompt" (per prompt) or "word" (average over prompts)
     # how the targeted latents are ranked: "corr" (EP:118-124: spike-mean activation x positive correlation with the
     # secret probability), or by what ablating the latent alone does at the spikes: "effect_lens" (the exact drop of

@@ -100,6 +100,14 @@ void tb_lowrank_edit(uint16_t* h, uint16_t* x_next, const uint8_t* apply, const 
                      int mmax, const void* E, const void* Dm, int table_f32, const float* bias, const float* thr,
                      const float* pre_bias, float alpha, const uint16_t* w_next, float eps, int M, int D,
                      float* coef_out, hipStream_t st, const float* val = nullptr);
+// matched_noise.hip: the norm-matched control of lowrank_edit (val null) / latent_affine_edit: the rows they would
+// edit move by n = |sum_j c_j Dm[idx_j]|_2 along z / |z|_2, z_d = rb_gauss(seeds[row], pos[row], d); rows they leave
+// alone stay bit-identical.  norm_out [M] (optional) = n, 0 on the untouched rows.
+void tb_matched_noise_edit(uint16_t* h, uint16_t* x_next, const uint8_t* apply, const int32_t* idx,
+                           const int32_t* cnt, int mmax, const void* E, const void* Dm, int table_f32,
+                           const float* bias, const float* thr, const float* pre_bias, float alpha,
+                           const uint16_t* w_next, float eps, int M, int D, float* coef_out, const float* val,
+                           const uint64_t* seeds, const int32_t* pos, float* norm_out, hipStream_t st);
 // reconstruct-mode splice: flagged rows h <- bf16(b_dec + sum_{a_j != 0, ascending j} s_j a_j W_dec[j]) with
 // a = acts[src_row[row]] (src_row null: acts[row]; out of [0, n_act_rows): row untouched), x_next = RMSNorm(h)
 void tb_sae_splice_edit(uint16_t* h, uint16_t* x_next, const uint8_t* apply, const int32_t* src_row,

@@ -732,13 +732,21 @@ void head_fused(torch::Tensor x, torch::Tensor W, torch::Tensor part, double cap
                  nll_self.data_ptr<float>(), np, M, N, K, cur_stream());
 }
 
-// lowrank_edit and, with val [M, mmax] fp32, latent_affine_edit (one kernel family, csrc/sae.hip)
+// What matched_noise_edit takes on top of lowrank_edit / latent_affine_edit
+struct NoiseArgs {
+  torch::Tensor seeds, pos;
+  c10::optional<torch::Tensor> norm_out;
+};
+
+// lowrank_edit and, with val [M, mmax] fp32, latent_affine_edit (one kernel family, csrc/sae.hip); with noise, the
+// norm-matched control of either (csrc/matched_noise.hip)
 static void lowrank_edit_impl(torch::Tensor h, c10::optional<torch::Tensor> x_next, torch::Tensor apply,
                               torch::Tensor idx, torch::Tensor cnt, torch::Tensor E, torch::Tensor Dm,
                               c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> thr,
                               c10::optional<torch::Tensor> pre_bias, double alpha,
                               c10::optional<torch::Tensor> w_next, double eps,
-                              c10::optional<torch::Tensor> coef_out, const torch::Tensor* val) {
+                              c10::optional<torch::Tensor> coef_out, const torch::Tensor* val,
+                              const NoiseArgs* noise = nullptr) {
   IN_BF16(h); IN_U8(apply); IN_I32(idx); IN_I32(cnt); CHECK_DEV(E); CHECK_CONTIG(E); CHECK_DEV(Dm);
   CHECK_CONTIG(Dm);
   TORCH_CHECK(E.scalar_type() == Dm.scalar_type(), "E/D dtype mismatch");
@@ -781,6 +789,25 @@ static void lowrank_edit_impl(torch::Tensor h, c10::optional<torch::Tensor> x_ne
     TORCH_CHECK(coef_out->numel() >= (int64_t)M * mmax, "lowrank_edit: coef_out smaller than [rows, mmax]");
     co = coef_out->data_ptr<float>();
   }
+  if (noise != nullptr) {
+    CHECK_DEV(noise->seeds); CHECK_CONTIG(noise->seeds); IN_I32(noise->pos);
+    TORCH_CHECK(noise->seeds.scalar_type() == at::kLong, "matched_noise_edit: seeds must be int64");
+    TORCH_CHECK(noise->seeds.numel() == M && noise->pos.numel() == M,
+                "matched_noise_edit: seeds and pos must be [rows]");
+    float* no = nullptr;
+    if (noise->norm_out.has_value() && noise->norm_out->defined()) {
+      IN_F32((*noise->norm_out));
+      TORCH_CHECK(noise->norm_out->numel() == M, "matched_noise_edit: norm_out must be [rows]");
+      no = noise->norm_out->data_ptr<float>();
+    }
+    c10::DeviceGuard g(h.device());
+    tb_matched_noise_edit(bf(h), xn, reinterpret_cast<const uint8_t*>(apply.data_ptr()), idx.data_ptr<int32_t>(),
+                          cnt.data_ptr<int32_t>(), mmax, E.data_ptr(), Dm.data_ptr(), f32 ? 1 : 0, optf(bias),
+                          optf(thr), optf(pre_bias), (float)alpha, wn, (float)eps, M, D, co, vp,
+                          reinterpret_cast<const uint64_t*>(noise->seeds.data_ptr<int64_t>()),
+                          noise->pos.data_ptr<int32_t>(), no, cur_stream());
+    return;
+  }
   c10::DeviceGuard g(h.device());
   tb_lowrank_edit(bf(h), xn, reinterpret_cast<const uint8_t*>(apply.data_ptr()), idx.data_ptr<int32_t>(),
                   cnt.data_ptr<int32_t>(), mmax, E.data_ptr(), Dm.data_ptr(), f32 ? 1 : 0, optf(bias), optf(thr),
@@ -801,6 +828,20 @@ void latent_affine_edit(torch::Tensor h, c10::optional<torch::Tensor> x_next, to
                         c10::optional<torch::Tensor> pre_bias, double alpha, c10::optional<torch::Tensor> w_next,
                         double eps, c10::optional<torch::Tensor> coef_out) {
   lowrank_edit_impl(h, x_next, apply, idx, cnt, E, Dm, bias, thr, pre_bias, alpha, w_next, eps, coef_out, &val);
+}
+
+// The norm-matched random-direction control of the two edits above: h += |delta|_2 z / |z|_2 on the rows they would
+// edit, z = rb_gauss(seeds[row], pos[row], .); val (optional) as in latent_affine_edit; norm_out [rows] = |delta|_2
+void matched_noise_edit(torch::Tensor h, c10::optional<torch::Tensor> x_next, torch::Tensor apply, torch::Tensor idx,
+                        torch::Tensor cnt, torch::Tensor E, torch::Tensor Dm, torch::Tensor seeds, torch::Tensor pos,
+                        c10::optional<torch::Tensor> val, c10::optional<torch::Tensor> bias,
+                        c10::optional<torch::Tensor> thr, c10::optional<torch::Tensor> pre_bias, double alpha,
+                        c10::optional<torch::Tensor> w_next, double eps, c10::optional<torch::Tensor> coef_out,
+                        c10::optional<torch::Tensor> norm_out) {
+  const NoiseArgs noise{seeds, pos, norm_out};
+  const bool aff = val.has_value() && val->defined();
+  lowrank_edit_impl(h, x_next, apply, idx, cnt, E, Dm, bias, thr, pre_bias, alpha, w_next, eps, coef_out,
+                    aff ? &*val : nullptr, &noise);
 }
 
 // Reconstruct-mode splice (csrc/sae.hip): acts [R, L] fp32 activation rows, src_row [M] int32 (optional) the
@@ -1202,6 +1243,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lens_gemm", &lens_gemm);
   m.def("lowrank_edit", &lowrank_edit);
   m.def("latent_affine_edit", &latent_affine_edit);
+  m.def("matched_noise_edit", &matched_noise_edit);
   m.def("sae_decode_sparse", &sae_decode_sparse);
   m.def("sae_splice_edit", &sae_splice_edit);
   m.def("flag_compact", &flag_compact);

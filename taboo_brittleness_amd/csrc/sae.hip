@@ -25,6 +25,7 @@
 //                   per prompt segment (EP:118-124).
 #include "common.h"
 #include "api.h"
+#include "lowrank_coef.h"
 
 namespace {
 
@@ -136,18 +137,7 @@ __global__ void __launch_bounds__(256) gemm_nt_kernel(const uint16_t* __restrict
 }
 
 // ---------------------------------------------------------------- low-rank edit
-template <typename TT>
-__device__ __forceinline__ void load8(const TT* p, float* f);
-template <>
-__device__ __forceinline__ void load8<uint16_t>(const uint16_t* p, float* f) {
-  unpack8(*reinterpret_cast<const uint4*>(p), f);
-}
-template <>
-__device__ __forceinline__ void load8<float>(const float* p, float* f) {
-  const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
-  f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-}
-
+// (load8 and the coefficient stage live in lowrank_coef.h, shared with matched_noise.hip)
 // One workgroup (256 threads) per row; D <= 256*8*VPT.  AFF (latent_affine_edit): the row's coefficient becomes
 // alpha * a_j - val[row, j] = -delta_j, so h += sum_j delta_j D_j moves latent j from alpha * a_j to val_j.  The two
 // entry points share every other line, so val == 0 gives lowrank_edit's bits.
@@ -163,7 +153,7 @@ __global__ void __launch_bounds__(256) lowrank_edit_kernel(
   __shared__ float red[16];
   __shared__ float coef[256];
   const int nvec = D >> 3;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int tid = threadIdx.x;
   uint16_t* hr = h + (size_t)row * D;
   float v[VPT][8];
 #pragma unroll
@@ -176,37 +166,9 @@ __global__ void __launch_bounds__(256) lowrank_edit_kernel(
   }
   const int m = min(cnt[row], min(mmax, 256));
   const int32_t* ir = idx + (size_t)row * mmax;
-  // coefficients: waves split the m directions, lanes split D
-  for (int j = wid; j < m; j += 4) {
-    const int e = ir[j];
-    const TT* er = E + (size_t)e * D;
-    float part = 0.f;
-    for (int c = lane; c < nvec; c += 64) {
-      float ef[8], hf[8];
-      load8<TT>(er + c * 8, ef);
-      unpack8(reinterpret_cast<const uint4*>(hr)[c], hf);
-      if (pre_bias) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) hf[q] -= pre_bias[c * 8 + q];
-      }
-#pragma unroll
-      for (int q = 0; q < 8; ++q) part += hf[q] * ef[q];
-    }
-    part = wave_sum(part);
-    if (lane == 0) {
-      float pre = part + (bias ? bias[e] : 0.f);
-      float a = pre;
-      if (thr) a = (pre > thr[e]) ? pre : 0.f;
-      coef[j] = alpha * a;
-      if (coef_out) coef_out[(size_t)row * mmax + j] = a;
-    }
-  }
-  __syncthreads();
-  if (AFF) {
-    // alpha * a_j went through LDS as an fp32 value, so the subtraction cannot contract with the product
-    if (tid < m) coef[tid] -= val[(size_t)row * mmax + tid];
-    __syncthreads();
-  }
+  lowrank_coefs<TT, AFF>(hr, ir, m, nvec, E, D, bias, thr, pre_bias, alpha,
+                         coef_out ? coef_out + (size_t)row * mmax : nullptr,
+                         AFF ? val + (size_t)row * mmax : nullptr, coef);
   // an all-zero edit (every ablated latent below its threshold here, or alpha = 0) is an exact no-op: h and
   // x_next stay bit-identical to the unedited forward (no re-rounded h, no re-normalised x)
   bool any = false;

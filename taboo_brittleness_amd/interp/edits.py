@@ -39,6 +39,13 @@ error-preserving kernel):
 An inactive latent is edited too, so a flagged row is a no-op only where
 ``alpha a_j == alpha c_j`` for every selected latent.  Same static shapes, no host
 sync; projection cells are unchanged.
+
+``sae_noise`` (kind 3) and ``proj_noise`` (kind 4) rows are the *norm-matched controls* of ``sae`` and ``proj``
+rows (``ops.matched_noise_edit``): at the same positions, the residual moves exactly as far as the targeted edit
+would move it (``|sum_j c_j D_j|_2``, the coefficients computed by the same device code), but along a Gaussian
+direction drawn from ``(EditPlan.seeds[row], absolute position)``.  A position therefore gets the same edit in a
+prefill, a teacher-forced tail and a decode step, and a row where the targeted edit is an exact no-op is one for
+the control too.  ``reconstruct`` replaces the residual instead of adding a delta to it, so it has no such control.
 """
 from __future__ import annotations
 
@@ -56,7 +63,7 @@ class EditPlan:
     """Device tensors, one row per sequence in the batch."""
 
     spikes: torch.Tensor                 # [B, K] int32 absolute positions, -1 = unused
-    kind: torch.Tensor                   # [B] int8: 0 none, 1 sae, 2 proj
+    kind: torch.Tensor                   # [B] int8: 0 none, 1 sae, 2 proj, 3 sae_noise, 4 proj_noise
     idx: torch.Tensor                    # [B, mmax] int32 (latent ids, or rows of the basis table)
     cnt: torch.Tensor                    # [B] int32
     alpha: float = 1.0
@@ -64,9 +71,19 @@ class EditPlan:
     mode: str = "error_preserving"         # sae cells: or "reconstruct" (splice the SAE reconstruction in)
     any_position: bool = False             # some row edits at ALL_POSITIONS (bounds the flagged rows of a forward)
     values: Optional[torch.Tensor] = None  # [B, mmax] fp32 targets c of the selected latents (clamp / steer modes)
+    seeds: Optional[torch.Tensor] = None   # [B] int64 noise streams of the sae_noise / proj_noise rows
+    has_noise: tuple = (False, False)      # host-known: some row has kind 3 / kind 4 (set by build)
 
     def __post_init__(self):
         check_mode(self.mode)
+        if any(self.has_noise):
+            if self.seeds is None:
+                raise ValueError("EditPlan: sae_noise / proj_noise rows need seeds ([B] int64)")
+            if self.has_noise[0] and self.mode == "reconstruct":
+                raise ValueError("EditPlan: sae_noise has no meaning under ablation_mode = reconstruct (the splice "
+                                 "replaces the residual: there is no added delta whose norm could be matched)")
+        if self.seeds is not None and (self.seeds.dtype != torch.int64 or self.seeds.numel() != self.kind.numel()):
+            raise ValueError("EditPlan.seeds must be [B] int64")
         if self.mode in AFFINE_MODES and self.values is None:
             self.values = torch.zeros(self.idx.shape, dtype=torch.float32, device=self.idx.device)
         if self.values is not None and tuple(self.values.shape) != tuple(self.idx.shape):
@@ -80,17 +97,19 @@ class EditPlan:
     @staticmethod
     def build(device, spikes: Sequence[Sequence[int]], kinds: Sequence[str], sel: Sequence[Sequence[int]],
               alpha: float = 1.0, basis: Optional[torch.Tensor] = None, kmax: Optional[int] = None,
-              mmax: Optional[int] = None, mode: str = "error_preserving", values=None) -> "EditPlan":
+              mmax: Optional[int] = None, mode: str = "error_preserving", values=None, seeds=None,
+              noise: Optional[tuple] = None) -> "EditPlan":
         """``values`` (clamp / steer modes): the targets of the selected latents, one scalar for all of them or a
-        per-row list of lists aligned with ``sel``."""
+        per-row list of lists aligned with ``sel``.  ``seeds``: one int per row, required with ``sae_noise`` /
+        ``proj_noise`` rows (taken mod 2^64).  ``noise``: which noise paths (``sae_noise``, ``proj_noise``) the hook
+        keeps, for a plan that is refilled in place; default: those of ``kinds``."""
         B = len(spikes)
         kmax = kmax or max(1, max((len(s) for s in spikes), default=1))
         mmax = mmax or max(1, max((len(s) for s in sel), default=1))
         sp = np.full((B, kmax), -1, dtype=np.int32)
         ix = np.zeros((B, mmax), dtype=np.int32)
         cn = np.zeros((B,), dtype=np.int32)
-        code = {"none": 0, "sae": 1, "proj": 2}
-        kd = np.asarray([code[k] for k in kinds], dtype=np.int8)
+        kd = np.asarray([KIND_CODES[k] for k in kinds], dtype=np.int8)
         for b in range(B):
             s = spikes[b]
             if len(s):
@@ -117,8 +136,22 @@ class EditPlan:
                     n = min(len(values[b]), mmax)
                     va[b, :n] = np.asarray(list(values[b])[:n], dtype=np.float32)
             vals = t(va)
+        sd = None
+        if seeds is not None:
+            if len(seeds) != B:
+                raise ValueError(f"EditPlan.build: seeds has {len(seeds)} rows, sel has {B}")
+            sd = t(seeds_to_int64(seeds))
         return EditPlan(t(sp), t(kd), t(ix), t(cn), alpha, basis.to(device) if basis is not None else None, mode,
-                        bool((sp == ALL_POSITIONS).any()), vals)
+                        bool((sp == ALL_POSITIONS).any()), vals, sd,
+                        tuple(noise) if noise is not None else (bool((kd == 3).any()), bool((kd == 4).any())))
+
+
+KIND_CODES = {"none": 0, "sae": 1, "proj": 2, "sae_noise": 3, "proj_noise": 4}
+
+
+def seeds_to_int64(seeds) -> np.ndarray:
+    """Python ints (any size) as the int64 array whose bits are the seeds mod 2^64 (the kernel reads them unsigned)."""
+    return np.asarray([int(s) & ((1 << 64) - 1) for s in seeds], dtype=np.uint64).view(np.int64)
 
 
 ALL_POSITIONS = -2   # spike value that matches every (non-padding) position: position-agnostic edits
@@ -179,6 +212,9 @@ class EditHook:
             }
             if self.plan.mode in AFFINE_MODES:
                 b["val"] = torch.empty(B * T, mmax, dtype=torch.float32, device=device)
+            if any(self.plan.has_noise):
+                b["apply_noise"] = torch.empty(B * T, dtype=torch.uint8, device=device)
+                b["seeds"] = torch.empty(B * T, dtype=torch.int64, device=device)
             if self.plan.mode == "reconstruct" and self.sae is not None:
                 b["src"] = torch.empty(B * T, dtype=torch.int32, device=device)
                 cap = self._capacity(B, T)
@@ -220,6 +256,34 @@ class EditHook:
         if pl.basis is not None:
             ops.lowrank_edit(h, r["apply_proj"], r["idx"], r["cnt"], pl.basis, pl.basis, None, None, None, 1.0,
                              ctx.w_next, ctx.eps, x, None)
+        if any(pl.has_noise):
+            self._noise(h, x, ctx, r, hit, kind, sl)
+
+    def _noise(self, h, x, ctx, r, hit, kind, sl) -> None:
+        """The norm-matched controls: kind-3 rows with the SAE tables (and the clamp / steer targets, built as for
+        the targeted rows), kind-4 rows with the plan's basis.  A row is flagged by one kind only, so the order of
+        the calls does not matter."""
+        B, T = ctx.B, ctx.T
+        pl = self.plan
+        r["seeds"].view(B, T).copy_(pl.seeds.index_select(0, sl).view(B, 1).expand(B, T))
+        pos = ctx.pos.view(B * T)
+        if pl.has_noise[0]:
+            if self.sae is None:
+                raise ValueError("EditPlan has sae_noise rows but the hook has no SAE")
+            s = self.sae
+            r["apply_noise"].copy_(hit & (kind == 3))
+            affine = pl.mode in AFFINE_MODES          # r["val"] was filled above, as for the targeted rows
+            alpha = 0.0 if pl.mode == "steer" else pl.alpha
+            ops.matched_noise_edit(h, r["apply_noise"], r["idx"], r["cnt"], s.W_encT, s.W_dec, r["seeds"], pos,
+                                   r["val"] if affine else None, s.b_enc, s.threshold,
+                                   s.b_dec if s.apply_b_dec_to_input else None, alpha, ctx.w_next, ctx.eps, x,
+                                   r["coef"])
+        if pl.has_noise[1]:
+            if pl.basis is None:
+                raise ValueError("EditPlan has proj_noise rows but no basis")
+            r["apply_noise"].copy_(hit & (kind == 4))
+            ops.matched_noise_edit(h, r["apply_noise"], r["idx"], r["cnt"], pl.basis, pl.basis, r["seeds"], pos,
+                                   None, None, None, None, 1.0, ctx.w_next, ctx.eps, x)
 
     def _capacity(self, B: int, T: int) -> int:
         """Host-known bound on the flagged rows of a ``[B, T]`` forward: a sequence is edited at no more than its

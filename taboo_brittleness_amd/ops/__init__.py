@@ -1030,6 +1030,24 @@ def latent_affine_edit(h, apply, idx, cnt, val, E, Dm, bias=None, thr=None, pre_
     return h
 
 
+def matched_noise_edit(h, apply, idx, cnt, E, Dm, seeds, pos, val=None, bias=None, thr=None, pre_bias=None, alpha=1.0,
+                       w_next=None, eps=1e-6, x_next=None, coef_out=None, norm_out=None):
+    """The norm-matched random-direction control of :func:`lowrank_edit` (``val`` None) and
+    :func:`latent_affine_edit` (``val [rows, mmax]`` fp32), in place: a flagged row that the targeted edit would move
+    by ``delta = sum_j c_j Dm[idx_j]`` (their coefficients, the same device code) moves by ``n = |delta|_2`` along
+    ``z / |z|_2`` instead, ``z_d = rb_gauss(seeds[row], pos[row], d)`` (``seeds [rows]`` int64, ``pos [rows]`` int32):
+    ``h <- bf16(h + n z / |z|)``, then ``x_next = RMSNorm(h, w_next)``.  A row whose coefficients are all zero (or
+    whose ``delta`` is) keeps ``h`` and ``x_next`` bit for bit.  A row's bits depend on its own inputs only.
+    ``coef_out`` receives ``a_j``, ``norm_out [rows]`` fp32 receives ``n`` (0 on every untouched row)."""
+    if h.is_cuda:
+        _k().matched_noise_edit(h, x_next, apply, idx, cnt, E, Dm, seeds, pos, val, bias, thr, pre_bias, float(alpha),
+                                w_next, float(eps), coef_out, norm_out)
+        return h
+    ref.matched_noise_edit(h, apply, idx, cnt, E, Dm, seeds, pos, val, bias, thr, pre_bias, alpha, w_next, eps, x_next,
+                           coef_out, norm_out)
+    return h
+
+
 def sae_splice_edit(h, apply, acts, idx, cnt, Wdec, b_dec=None, alpha=1.0, w_next=None, eps=1e-6, x_next=None,
                     src_row=None):
     """Reconstruct-mode SAE ablation, in place: per flagged row ``h <- bf16(b_dec + sum_{a_j != 0, ascending j}

@@ -356,6 +356,51 @@ def latent_affine_edit(h: torch.Tensor, apply: torch.Tensor, idx: torch.Tensor, 
             x_next.view(-1, D)[r] = rmsnorm(hv[r:r + 1], w_next, eps)[0]
 
 
+def matched_noise_edit(h: torch.Tensor, apply: torch.Tensor, idx: torch.Tensor, cnt: torch.Tensor, E: torch.Tensor,
+                       Dm: torch.Tensor, seeds: torch.Tensor, pos: torch.Tensor, val: Optional[torch.Tensor] = None,
+                       bias=None, thr=None, pre_bias=None, alpha: float = 1.0,
+                       w_next: Optional[torch.Tensor] = None, eps: float = 1e-6,
+                       x_next: Optional[torch.Tensor] = None, coef_out: Optional[torch.Tensor] = None,
+                       norm_out: Optional[torch.Tensor] = None) -> None:
+    """The norm-matched control of :func:`lowrank_edit` (``val`` None) / :func:`latent_affine_edit`: a row they would
+    edit by ``-delta``, ``delta = c @ Dm[sel]`` (fp32), becomes ``bf16(h + n z / |z|)`` with ``n = |delta|_2`` and
+    ``z = rb_gauss(seeds[row], pos[row], .)`` (fp64); rows they leave alone (and rows with ``n == 0``) are left
+    untouched.  ``norm_out [rows]`` receives ``n`` (0 on the untouched rows), ``coef_out`` the ``a_j``."""
+    D = h.shape[-1]
+    hv = h.view(-1, D)
+    M = hv.shape[0]
+    mmax = idx.numel() // M
+    iv = idx.view(M, mmax)
+    vv = val.view(M, mmax).float() if val is not None else None
+    if norm_out is not None:
+        norm_out.zero_()
+    for r in torch.nonzero(apply.view(-1).bool()).flatten().tolist():
+        m = max(0, min(int(cnt.view(-1)[r]), mmax, 256))
+        sel = iv[r, :m].long()
+        x = hv[r].float()
+        xb = x - pre_bias.float() if pre_bias is not None else x
+        pre = E[sel].float() @ xb
+        if bias is not None:
+            pre = pre + bias.float()[sel]
+        a = torch.where(pre > thr.float()[sel], pre, torch.zeros_like(pre)) if thr is not None else pre
+        if coef_out is not None:
+            coef_out.view(M, mmax)[r, :m] = a
+        c = alpha * a - vv[r, :m] if vv is not None else alpha * a
+        if not bool((c != 0).any()):
+            continue                      # where the targeted edit is an exact no-op, so is its control
+        delta = c @ Dm[sel].float()
+        n = float(torch.linalg.vector_norm(delta.double()).float())
+        if not n > 0.0:
+            continue
+        z = rb_gauss(int(seeds.view(-1)[r]), int(pos.view(-1)[r]), D)
+        step = torch.from_numpy((n / np.sqrt(np.sum(z * z)) * z).astype(np.float32))
+        hv[r] = rbf(x + step).to(h.dtype)
+        if norm_out is not None:
+            norm_out.view(-1)[r] = n
+        if x_next is not None and w_next is not None:
+            x_next.view(-1, D)[r] = rmsnorm(hv[r:r + 1], w_next, eps)[0]
+
+
 def sae_splice_edit(h: torch.Tensor, apply: torch.Tensor, acts: torch.Tensor, idx: torch.Tensor, cnt: torch.Tensor,
                     Wdec: torch.Tensor, b_dec: Optional[torch.Tensor] = None, alpha: float = 1.0,
                     w_next: Optional[torch.Tensor] = None, eps: float = 1e-6, x_next: Optional[torch.Tensor] = None,
@@ -530,19 +575,26 @@ def _rb_mix64(z):
     return z ^ (z >> np.uint64(31))
 
 
-def random_basis(D: int, r: int, seed: int) -> np.ndarray:
-    """csrc/basis.hip in numpy: ``[r, D]`` fp32 orthonormal rows.  Entry ``(j, d)`` of the Gaussian is Box-Muller of
-    two splitmix64 hashes of ``seed * phi + (j << 32 | d)``; row ``j`` is orthonormalised by classical Gram-Schmidt
-    applied twice (64 earlier rows per chunk), in fp64, against the fp32-rounded rows before it.  (The kernel's dot products sum in another order: rows agree to
-    fp32 rounding, not bit for bit.)"""
-    j = np.arange(r, dtype=np.uint64)[:, None]
+def rb_gauss(seed: int, j, D: int) -> np.ndarray:
+    """Rows ``j`` (an int or an array of them) of the counter-hash Gaussian of csrc/rb_gauss.h: ``[len(j), D]`` (or
+    ``[D]``) fp64, entry ``(j, d)`` = Box-Muller of two splitmix64 hashes of ``seed * phi + (j << 32 | d)``."""
+    jj = (np.atleast_1d(np.asarray(j, dtype=np.int64)).astype(np.uint64) & np.uint64(0xFFFFFFFF))[:, None]
     d = np.arange(D, dtype=np.uint64)[None, :]
     with np.errstate(over="ignore"):
-        key = np.uint64(int(seed) & ((1 << 64) - 1)) * _RB_G + ((j << np.uint64(32)) | d)
+        key = np.uint64(int(seed) & ((1 << 64) - 1)) * _RB_G + ((jj << np.uint64(32)) | d)
         a, b = _rb_mix64(key), _rb_mix64(key ^ _RB_X)
     u1 = ((a >> np.uint64(11)).astype(np.float64) + 1.0) * 2.0 ** -53
     u2 = (b >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
     G = np.sqrt(-2.0 * np.log(u1)) * np.cos(6.283185307179586 * u2)
+    return G if np.ndim(j) else G[0]
+
+
+def random_basis(D: int, r: int, seed: int) -> np.ndarray:
+    """csrc/basis.hip in numpy: ``[r, D]`` fp32 orthonormal rows.  Row ``j`` of the Gaussian is :func:`rb_gauss`;
+    it is orthonormalised by classical Gram-Schmidt applied twice (64 earlier rows per chunk), in fp64, against the
+    fp32-rounded rows before it.  (The kernel's dot products sum in another order: rows agree to fp32 rounding, not
+    bit for bit.)"""
+    G = rb_gauss(seed, np.arange(r), D)
     Q = np.zeros((r, D), np.float32)
     Qd = np.zeros((r, D), np.float64)
     for jj in range(r):

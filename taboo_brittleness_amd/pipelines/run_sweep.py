@@ -25,7 +25,7 @@ from ..config import Config
 from ..parallel import dist as D
 from ..utils.io import atomic_write_json, atomic_write_text
 from .factory import build_stack
-from .sweep import METHODS, SweepRunner, summarize_cells
+from .sweep import METHODS, NOISE_METHODS, SweepRunner, summarize_cells
 
 
 def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info: Optional[D.DistInfo] = None,
@@ -142,6 +142,8 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
             summary["config"]["clamp_value"] = runner.clamp_value
         if causal:
             summary["config"]["latent_score"] = runner.latent_score
+        if any(m in NOISE_METHODS for m in methods):
+            summary["config"]["noise_trials"] = cfg.intervention.noise_trials
         if forcing is not None:
             summary["forcing"] = forcing
         os.makedirs(out_dir, exist_ok=True)
@@ -235,7 +237,14 @@ def forcing_curves(cfg: Config, runner: SweepRunner, pairs, methods: Sequence[st
                 for m in iv.budgets:
                     tl = word_targeted_latents(runner, w, m)
                     trials = 1 if meth == "sae_targeted" else max(1, iv.forcing_trials or iv.random_trials)
+                    if meth == "sae_noise":
+                        trials = max(1, iv.forcing_trials or iv.noise_trials)
                     for t in range(trials):
+                        if meth == "sae_noise":       # the targeted latents' norm, a random direction per position
+                            settings.append({"word": w, "kind": "sae_noise", "latents": tl, "alpha": iv.alpha,
+                                             "seed": A.cell_seed("forcing", w, meth, m, t)})
+                            keys.append((meth, m))
+                            continue
                         lat = tl if meth == "sae_targeted" else A.random_latents(
                             runner.sae.d_sae, m, A.cell_seed("forcing", w, meth, m, t), exclude=tl, pool=pool)
                         settings.append({"word": w, "kind": "sae", "latents": lat, "alpha": iv.alpha})
@@ -244,7 +253,14 @@ def forcing_curves(cfg: Config, runner: SweepRunner, pairs, methods: Sequence[st
                 key = w if iv.pca_pool == "word" else "__all__"
                 for r in iv.ranks:
                     trials = 1 if meth == "proj_targeted" else max(1, iv.forcing_trials or iv.proj_random_trials)
+                    if meth == "proj_noise":
+                        trials = max(1, iv.forcing_trials or iv.noise_trials) if key in bases else 0
                     for t in range(trials):
+                        if meth == "proj_noise":
+                            settings.append({"word": w, "kind": "proj_noise", "basis": bases[key][:r].to(runner.dev),
+                                             "seed": A.cell_seed("forcing", w, meth, r, t)})
+                            keys.append((meth, r))
+                            continue
                         U = bases[key][:r] if meth == "proj_targeted" and key in bases else \
                             A.random_subspace(runner.D, r, A.cell_seed("forcing", w, meth, r, t), device=runner.dev)
                         settings.append({"word": w, "kind": "proj", "basis": U.to(runner.dev)})

@@ -83,9 +83,10 @@ from ..runtime.generation import Generator
 from .sweep_decode import DecodeMixin
 from .sweep_plan import PlanMixin
 from .sweep_readout import ReadoutMixin
-from .sweep_types import METHODS, Cell, NextBatch, Pair, _Carry, _Deferred
+from .sweep_types import METHODS, NOISE_METHODS, Cell, NextBatch, Pair, _Carry, _Deferred
 
-__all__ = ["METHODS", "Pair", "Cell", "NextBatch", "SweepRunner", "word_targeted_latents", "summarize_cells"]
+__all__ = ["METHODS", "NOISE_METHODS", "Pair", "Cell", "NextBatch", "SweepRunner", "word_targeted_latents",
+           "summarize_cells"]
 
 
 class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
@@ -156,6 +157,7 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
         self._drain = True
         self._drain_batch = True
         self._with_basis = True
+        self._with_noise = (False, False)             # the persistent plan has the (sae_noise, proj_noise) paths
 
     # ----------------------------------------------------------------- pairs
     def build_pairs(self, words: Sequence[str], prompts: Sequence[str]) -> List[Pair]:
@@ -289,6 +291,18 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
             self._plan = None                                # plan layout changes: rebuild + recapture
             self.gen.invalidate_graph()
             self._with_basis = True
+        noise = self._noise_kinds(cells)
+        if self._plan is None:
+            self._with_noise = noise
+        elif any(w and not h for w, h in zip(noise, self._plan.has_noise)):
+            # first noise cells of this runner: the plan gains the noise path (rebuild + recapture, as for a basis)
+            assert not self._carry, "carried cells live in the old plan: drain before the first noise cells"
+            self._with_noise = tuple(w or h for w, h in zip(noise, self._plan.has_noise))
+            self._with_basis = self._plan.basis is not None
+            self._plan = None
+            self.gen.invalidate_graph()
+        if any(noise):
+            self._edit_norms(pairs, cells, bases)
         per = self.B - len(ride)
         assert per > 0 or not cells, "batch too small for the ride-along baselines"
         parts = []
@@ -373,5 +387,7 @@ def summarize_cells(results: Sequence[dict], words: Sequence[str], word_plurals:
                     preds.setdefault(r["word"], []).append(r["guesses"])
             per_trial.append(calculate_metrics(preds, list(words), word_plurals)["overall"])
         ent["ll_topk"] = {k: float(np.mean([m[k] for m in per_trial])) for k in per_trial[0]} if per_trial else {}
+        if meth in NOISE_METHODS:                # how far the control (= its targeted twin) moved the stream
+            ent["edit_norm"] = float(np.mean([r["edit_norm"] for r in rs]))
         curves.append(ent)
     return {"curves": curves}

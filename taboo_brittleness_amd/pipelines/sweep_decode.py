@@ -477,17 +477,18 @@ class DecodeMixin:
                 src = b
                 d, nll = D[b], nll_c[b]
                 pre = (p.kv_slot, p.plen + D[b], p.plen + f)
-                prow = (plan["spikes"][b].copy(), int(plan["kind"][b]), plan["idx"][b].copy(), int(plan["cnt"][b]))
+                prow = (plan["spikes"][b].copy(), int(plan["kind"][b]), plan["idx"][b].copy(), int(plan["cnt"][b]),
+                        int(plan["seeds"][b]))
             else:
                 cr = obj
                 c, p, src, d, nll, pre = cr.cell, cr.pair, cr.slot, cr.d, cr.nll, cr.pre
                 prow = cr.plan_row if kind != "new" else prow
-            if prow[1] == 2:       # projection cell: its basis rows move with it
+            if prow[1] in (2, 4):  # projection cell (or its norm-matched control): its basis rows move with it
                 ix = prow[2].copy()
                 ix[: prow[3]] = np.arange(dst * rmax, dst * rmax + prow[3])
                 b_src += prow[2][: prow[3]].tolist()
                 b_dst += list(range(dst * rmax, dst * rmax + prow[3]))
-                prow = (prow[0], prow[1], ix, prow[3])
+                prow = (prow[0], prow[1], ix, prow[3], prow[4])
             self._carry.append(_Carry(c, p, d, nll, dst, int(st["tok"][k]), int(st["pos"][k]),
                                       st["tokens"][k, :step].tolist(), st["nll"][k, :step].astype(np.float32),
                                       int(rsteps[n_ride_rows + j] - ran), pre, prow))

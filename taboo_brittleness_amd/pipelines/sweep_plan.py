@@ -15,7 +15,7 @@ import torch
 from .. import ops
 from ..interp import analysis as A
 from ..interp.edits import EditHook, EditPlan
-from .sweep_types import METHODS, SPLICE_METHOD, Cell, NextBatch, Pair, _h2d
+from .sweep_types import METHODS, NOISE_METHODS, SPLICE_METHOD, Cell, NextBatch, Pair, _h2d
 
 
 class PlanMixin:
@@ -204,10 +204,90 @@ class PlanMixin:
         for i, (g, k, c0, m) in enumerate(owner):
             live[g].act_mask[c0:c0 + m] |= nz[i, :m].astype(np.int64) << k
 
+    @staticmethod
+    def _noise_kinds(cells: Sequence[Cell]) -> Tuple[bool, bool]:
+        ms = {c.method for c in cells}
+        return ("sae_noise" in ms, "proj_noise" in ms)
+
+    @torch.no_grad()
+    def _edit_norms(self, pairs: Sequence[Pair], cells: Sequence[Cell], bases: Dict[str, torch.Tensor]) -> None:
+        """How far the norm-matched controls move the stream: per (pair, noise method, budget), the mean over the
+        pair's spikes of ``|targeted delta|_2 / |h|_2``, measured by the control's own kernel
+        (``ops.matched_noise_edit``'s ``norm_out``) on copies of the baseline's hooked-layer residuals at the spikes
+        -- the rows the teacher-forced tail edits.  Kept on the pair (``Pair.edit_norm``) until it is re-baselined;
+        result records of noise cells carry it as ``edit_norm``."""
+        K, s, dev = self.iv.spikes_k, self.sae, self.dev
+        rows: Dict[str, list] = {"sae_noise": [], "proj_noise": []}       # (pair, budget, latent ids | basis rows)
+        for c in cells:
+            if c.method not in NOISE_METHODS:
+                continue
+            p = pairs[c.pair]
+            if p.edit_norm is None or p.edit_norm[0] is not p.resid:
+                p.edit_norm = (p.resid, {})
+            if (c.method, c.budget) in p.edit_norm[1]:
+                continue
+            p.edit_norm[1][(c.method, c.budget)] = 0.0
+            if p.resid is None or not [t for t in p.spikes_rel[:K] if 0 <= t < p.resid.shape[0]]:
+                continue
+            if c.method == "sae_noise":
+                rows[c.method].append((p, c.budget, list(p.targeted[: c.budget]), None))
+            else:
+                bk = p.word if self.iv.pca_pool == "word" else "__all__"
+                rows[c.method].append((p, c.budget, None, bases[bk][: c.budget]))
+        for meth, ent in rows.items():
+            if not ent:
+                continue
+            hs, ix, own, tabs, off = [], [], [], [], 0
+            for p, bud, lat, U in ent:
+                if U is not None:                    # this entry's basis rows, appended to the call's table
+                    lat = list(range(off, off + int(U.shape[0])))
+                    tabs.append(U.float().to(dev))
+                    off += int(U.shape[0])
+                for t in p.spikes_rel[:K]:
+                    if 0 <= t < p.resid.shape[0]:
+                        hs.append(p.resid[t])
+                        ix.append(lat)
+                        own.append((p, bud))
+            n, mmax = len(hs), max(1, max(len(l) for l in ix))
+            idx = np.zeros((n, mmax), np.int32)
+            for i, l in enumerate(ix):
+                idx[i, :len(l)] = l
+            h = torch.stack(hs).contiguous()
+            hn = torch.linalg.vector_norm(h.float(), dim=1)
+            # the norm does not depend on the draw: any stream will do
+            seeds = torch.zeros(n, dtype=torch.int64, device=dev)
+            pos = torch.zeros(n, dtype=torch.int32, device=dev)
+            norm = torch.zeros(n, dtype=torch.float32, device=dev)
+            ap = torch.ones(n, dtype=torch.uint8, device=dev)
+            idx_d = torch.from_numpy(idx).to(dev)
+            cnt_d = torch.tensor([len(l) for l in ix], dtype=torch.int32, device=dev)
+            if meth == "sae_noise":
+                # the coefficients of the sweep's own edit: clamp -> val = alpha c, steer -> val = c at alpha 0
+                val, alpha = None, self.iv.alpha
+                if self.affine:
+                    alpha = self.iv.alpha if self.ablation_mode == "clamp" else 0.0
+                    val = torch.full((n, mmax), self.clamp_value, dtype=torch.float32, device=dev)
+                    val = val * alpha if self.ablation_mode == "clamp" else val
+                ops.matched_noise_edit(h, ap, idx_d, cnt_d, s.W_encT, s.W_dec, seeds, pos, val,
+                                       s.b_enc, s.threshold, s.b_dec if s.apply_b_dec_to_input else None, alpha,
+                                       norm_out=norm)
+            else:
+                tab = torch.cat(tabs, 0).contiguous()
+                ops.matched_noise_edit(h, ap, idx_d, cnt_d, tab, tab, seeds, pos, norm_out=norm)
+            rel = (norm / hn.clamp_min(1e-30)).cpu().numpy()
+            acc: Dict[tuple, list] = {}
+            for i, (p, bud) in enumerate(own):
+                acc.setdefault((id(p), bud), [p]).append(float(rel[i]))
+            for (_, bud), v in acc.items():
+                v[0].edit_norm[1][(meth, bud)] = float(np.mean(v[1:]))
+
     # ----------------------------------------------------------------- cells
     def make_cells(self, pairs: Sequence[Pair], methods: Sequence[str] = METHODS) -> List[Cell]:
         cells: List[Cell] = []
         base = self.cfg.experiment.seed
+        if "sae_noise" in methods and self.ablation_mode == "reconstruct":
+            raise ValueError("sae_noise has no meaning under ablation_mode = reconstruct: the splice replaces the "
+                             "residual, so there is no added delta whose norm could be matched")
         for pi, p in enumerate(pairs):
             for meth in methods:
                 if meth == SPLICE_METHOD:
@@ -218,6 +298,8 @@ class PlanMixin:
                     budgets, trials = self.iv.budgets, (1 if meth == "sae_targeted" else self.iv.random_trials)
                 else:
                     budgets, trials = self.iv.ranks, (1 if meth == "proj_targeted" else self.iv.proj_random_trials)
+                if meth in NOISE_METHODS:
+                    trials = self.iv.noise_trials
                 for bud in budgets:
                     for t in range(trials):
                         # replicate 0 keeps the plain key, so sweeps seeded before replicates existed reproduce;
@@ -288,6 +370,7 @@ class PlanMixin:
         ix = np.zeros((B, mmax), dtype=np.int32)
         cn = np.zeros(B, dtype=np.int32)
         kd = np.zeros(B, dtype=np.int8)
+        sd = np.zeros(B, dtype=np.int64)                   # noise streams of the sae_noise / proj_noise rows
         tgt: Dict[str, Tuple[List[int], List[int]]] = {}   # pooled basis -> (table rows, its rows)
         rproj: Tuple[List[int], List[int], List[int]] = ([], [], [])   # random controls: (first row, rank, seed)
         by_pair: Dict[int, List[int]] = {}
@@ -299,7 +382,8 @@ class PlanMixin:
             ca = np.asarray(cis)
             if s_abs:
                 sp[ca, : len(s_abs)] = s_abs
-            rnd = [ci for ci in cis if cells[ci].kind == "sae" and cells[ci].method not in ("sae_targeted", SPLICE_METHOD)]
+            rnd = [ci for ci in cis if cells[ci].kind == "sae" and
+                   cells[ci].method not in ("sae_targeted", "sae_noise", SPLICE_METHOD)]
             if rnd:
                 got = A.random_latents_batch(self.sae.d_sae, [cells[ci].budget for ci in rnd],
                                              [cells[ci].seed for ci in rnd],
@@ -312,15 +396,18 @@ class PlanMixin:
             for ci in cis:
                 c = cells[ci]
                 if c.kind == "sae":
-                    if c.method == "sae_targeted":
+                    if c.method in ("sae_targeted", "sae_noise"):     # the control takes the targeted cell's latents
                         n = min(c.budget, tg.size)
                         ix[ci, :n] = tg[:n]
                         cn[ci] = n
-                        kd[ci] = 1
+                        if c.method == "sae_targeted":
+                            kd[ci] = 1
+                        else:
+                            kd[ci], sd[ci] = 3, c.seed
                     elif c.method == SPLICE_METHOD:
                         kd[ci] = 1                   # nothing ablated (cnt 0): the row is spliced as it is
                 else:
-                    if c.method == "proj_targeted":
+                    if c.method in ("proj_targeted", "proj_noise"):   # ... and the targeted cell's basis rows
                         bk = p.word if self.iv.pca_pool == "word" else "__all__"
                         r = min(c.budget, int(bases[bk].shape[0]))
                         dst, src = tgt.setdefault(bk, ([], []))
@@ -334,6 +421,8 @@ class PlanMixin:
                     ix[ci, :r] = np.arange(ci * rmax, ci * rmax + r)
                     cn[ci] = r
                     kd[ci] = 2
+                    if c.method == "proj_noise":
+                        kd[ci], sd[ci] = 4, c.seed
         basis = None
         # largest rank first (a basis costs ~r^2 block reductions; the workgroups are dispatched in order)
         lpt = np.argsort(-np.asarray(rproj[1], np.int64), kind="stable")
@@ -341,7 +430,8 @@ class PlanMixin:
             basis = {"tgt": {k: (np.asarray(d, np.int64), np.asarray(sr, np.int64)) for k, (d, sr) in tgt.items()},
                      "bases": {k: bases[k] for k in tgt},
                      "rnd": tuple(np.asarray(v, t)[lpt] for v, t in zip(rproj, (np.int64, np.int32, np.int64)))}
-        plan = {"spikes": sp, "kind": kd, "idx": ix, "cnt": cn, "basis": basis, "rows": B * rmax, "rmax": rmax,
+        plan = {"spikes": sp, "kind": kd, "idx": ix, "cnt": cn, "seeds": sd, "basis": basis, "rows": B * rmax,
+                "rmax": rmax,
                 "f": self._effective_first_edit(cells, pairs, by_pair, kd, ix, cn)}
         return self._plan_add_carry(plan) if with_carry else plan
 
@@ -357,7 +447,8 @@ class PlanMixin:
     def _effective_first_edit(self, cells, pairs, by_pair, kd, ix, cn) -> np.ndarray:
         """Per cell (plan row): response index of its first spike where the edit is non-zero (the pair's spike
         order), ``len(resp)`` if it never is (the cell is its baseline), -1 = the pair's first spike (projection
-        cells, or no activity table).  Latents outside a pair's activity table count as active everywhere."""
+        cells, or no activity table).  Latents outside a pair's activity table count as active everywhere.  A
+        ``sae_noise`` row (kind 3) is zero exactly where its targeted twin is."""
         K = self.iv.spikes_k
         f = np.full(self.B, -1, np.int64)
         if not self.skip_noop_spikes or self.ablation_mode == "reconstruct" or self.affine:
@@ -370,7 +461,7 @@ class PlanMixin:
             if p.act_key != key:
                 continue                        # stale or missing table: every cell edits from the first spike
             sp = np.asarray(p.spikes_rel[:K], np.int64)
-            ca = np.asarray([ci for ci in cis if kd[ci] == 1], np.int64)
+            ca = np.asarray([ci for ci in cis if kd[ci] == 1 or kd[ci] == 3], np.int64)
             if ids is None or not ca.size or not sp.size:
                 continue
             lat = ix[ca].astype(np.int64)
@@ -386,11 +477,12 @@ class PlanMixin:
 
     def _plan_add_carry(self, plan: dict) -> dict:
         for cr in self._carry:                  # carried cells keep editing at their carry-region slots
-            cs_, ck_, ci_, cc_ = cr.plan_row
+            cs_, ck_, ci_, cc_, sd_ = cr.plan_row
             plan["spikes"][cr.slot] = cs_
             plan["kind"][cr.slot] = ck_
             plan["idx"][cr.slot] = ci_
             plan["cnt"][cr.slot] = cc_
+            plan["seeds"][cr.slot] = sd_
         return plan
 
     def prefetch(self, pairs: Sequence[Pair], methods: Sequence[str] = METHODS):
@@ -433,11 +525,15 @@ class PlanMixin:
             # clamp / steer: every selected latent has the same target, so the plan's values never change
             values = torch.full(plan["idx"].shape, self.clamp_value, dtype=torch.float32, device=dev) \
                 if self.affine else None
+            # the noise paths exist only in a plan built for a call with noise cells (self._with_noise): every other
+            # sweep runs the kernels it ran before
+            noise = tuple(self._with_noise)
             self._plan = EditPlan(t(plan["spikes"]), t(plan["kind"]), t(plan["idx"]), t(plan["cnt"]), self.iv.alpha,
-                                  basis, self.ablation_mode, values=values)
+                                  basis, self.ablation_mode, values=values,
+                                  seeds=t(plan["seeds"]) if any(noise) else None, has_noise=noise)
             self._hook = EditHook(self._plan, self.sae)
         else:
-            for f in ("spikes", "kind", "idx", "cnt"):
+            for f in ("spikes", "kind", "idx", "cnt") + (("seeds",) if self._plan.seeds is not None else ()):
                 getattr(self._plan, f).copy_(_h2d(plan[f], dev), non_blocking=True)
         if plan["basis"] is not None:
             assert self._plan.basis is not None, "projection cells need a plan built with a basis table"
@@ -480,6 +576,8 @@ class PlanMixin:
         if not nb.cells or len(nb.cells) > self.B or not self._resumable(cp) or \
                 (proj and (self._plan is None or self._plan.basis is None)):
             return
+        if self._plan is None or any(w and not h for w, h in zip(self._noise_kinds(nb.cells), self._plan.has_noise)):
+            return                               # the plan has no noise path yet: run_cells rebuilds it
         if nb.plan is None:      # bases pooled over the call's pairs, as run_cells computes them
             nb.plan = self._plan_for(nb.cells, nb.pairs, self._bases(nb.pairs) if proj else {}, with_carry=False)
         plan = nb.plan

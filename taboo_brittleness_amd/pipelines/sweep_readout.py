@@ -15,7 +15,7 @@ from ..interp import analysis as A
 from ..interp.edits import EditHook
 from ..interp.logit_lens import excl_table, lens_packed, lens_readout, reference_exclusions, vocab_slice, vocab_topk
 from ..interp.prompts import contains_secret
-from .sweep_types import Cell, Pair, _h2d, _nullctx
+from .sweep_types import NOISE_METHODS, Cell, Pair, _h2d, _nullctx
 
 # bf16 logits per vocab-head GEMM chunk of the teacher-forced tail: 2 GB (4096 rows) measured +0.65 % over 1 GB at the
 # same 263 GB peak; 4 GB +0.3 % more but 276 GB peak (profiles/r5/bench/head_chunk/)
@@ -544,7 +544,7 @@ class ReadoutMixin:
         if p.p_secret_mean is None:
             p.p_secret_mean = float(p.p_secret.mean()) if p.p_secret is not None and p.p_secret.size else 0.0
             p.forms_l = {f.lower() for f in p.forms}
-        return {
+        rec = {
             "word": p.word, "prompt_idx": p.pidx, "method": c.method, "budget": c.budget, "trial": c.trial,
             "seed": c.seed, "n_gen": n_gen, "spikes": p.spikes_rel,
             "p_secret_mean": stats[0], "p_secret_final": stats[1], "p_secret_max": stats[2],
@@ -557,6 +557,9 @@ class ReadoutMixin:
             "nll_self": nll_self,
             "response_ids": resp,
         }
+        if c.method in NOISE_METHODS:            # norm-matched controls only: the other records keep their keys
+            rec["edit_norm"] = p.edit_norm[1][(c.method, c.budget)]
+        return rec
 
     def _nll_ws(self, M: int, key: int = 0):
         """Workspace for the ragged passes (one per stream ``key``), grown in 4096-row steps and sliced

@@ -14,6 +14,10 @@ METHODS = ("sae_targeted", "sae_random", "proj_targeted", "proj_random")
 # reconstruction with nothing ablated (budget 0, one cell per pair), the control that separates "the SAE error was
 # dropped" from "these latents were removed"
 SPLICE_METHOD = "sae_splice"
+# norm-matched controls (opt-in, never part of METHODS): the cell of ``sae_targeted`` / ``proj_targeted`` at the same
+# budget / rank, whose residual moves exactly as far at the same positions but along a seeded random direction
+# (ops.matched_noise_edit); ``intervention.noise_trials`` cells per budget / rank
+NOISE_METHODS = ("sae_noise", "proj_noise")
 
 
 @dataclass
@@ -56,6 +60,9 @@ class Pair:
     targeted_scores: Optional[List[float]] = None
     targeted_corr: Optional[List[int]] = None
     score_grads: Optional[tuple] = None
+    # norm-matched controls only: (the baseline residuals the figures were taken from, {(method, budget): mean over
+    # the spikes of |targeted delta|_2 / |h|_2}) -- SweepRunner._edit_norms
+    edit_norm: Optional[tuple] = None
 
     @property
     def first_edit(self) -> int:
@@ -101,7 +108,7 @@ class _Carry:
     prefix_nll: np.ndarray       # their NLLs
     steps: int                   # decode steps still needed
     pre: Tuple[int, int, int]    # (pair KV slot, len_lo, len_hi) of the shared prefix
-    plan_row: Tuple[np.ndarray, int, np.ndarray, int]   # host (spikes, kind, idx, cnt) of the slot
+    plan_row: Tuple[np.ndarray, int, np.ndarray, int, int]   # host (spikes, kind, idx, cnt, noise seed) of the slot
 
 
 class NextBatch:

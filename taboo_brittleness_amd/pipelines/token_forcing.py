@@ -24,12 +24,15 @@ import numpy as np
 import torch
 
 from ..config import Config
-from ..interp.edits import AFFINE_MODES, ALL_POSITIONS, EditHook, EditPlan, check_mode
+from ..interp.edits import AFFINE_MODES, ALL_POSITIONS, EditHook, EditPlan, check_mode, seeds_to_int64
 from ..interp.prompts import contains_secret, conversation_ids, pregame_ids
 from ..metrics import calculate_metrics
 from ..runtime.generation import Generator
 
 _WORD = re.compile(r"[A-Za-z']+")
+# setting / edit kinds that act through the SAE, and through a projection basis; the ``*_noise`` kinds are the
+# norm-matched controls of the other two (``"seed"``: their noise stream; the draw also depends on the position)
+SAE_KINDS, PROJ_KINDS = ("sae", "sae_noise"), ("proj", "proj_noise")
 
 
 class DPShard:
@@ -64,7 +67,7 @@ def first_word(text: str) -> str:
 def setting_value(mode: str, st: Optional[Dict], default: float) -> Optional[float]:
     """The clamp / steer target of an SAE setting or edit: its ``"value"``, else ``intervention.clamp_value``
     (``default``); None in the other modes and for other kinds.  A ``steer`` edit that adds 0 is rejected."""
-    if mode not in AFFINE_MODES or not st or st.get("kind", "sae") != "sae":
+    if mode not in AFFINE_MODES or not st or st.get("kind", "sae") not in SAE_KINDS:
         return None
     v = float(st.get("value", default))
     check_mode(mode, v)
@@ -75,11 +78,12 @@ def _hooks_for(B: int, layer: int, sae, edit: Optional[Dict], device,
                mode: str = "error_preserving", value: Optional[float] = None) -> Optional[Dict[int, list]]:
     if not edit:
         return None
-    kinds = [edit.get("kind", "sae")] * B
-    sel = [list(edit["latents"] if edit.get("kind", "sae") == "sae" else range(edit["basis"].shape[0]))] * B
-    plan = EditPlan.build(device, [[ALL_POSITIONS]] * B, kinds, sel, alpha=edit.get("alpha", 1.0),
-                          basis=edit.get("basis"), mode=mode, values=value)
-    return {layer: [EditHook(plan, sae if edit.get("kind", "sae") == "sae" else None)]}
+    kind = edit.get("kind", "sae")
+    sel = [list(edit["latents"] if kind in SAE_KINDS else range(edit["basis"].shape[0]))] * B
+    plan = EditPlan.build(device, [[ALL_POSITIONS]] * B, [kind] * B, sel, alpha=edit.get("alpha", 1.0),
+                          basis=edit.get("basis"), mode=mode, values=value,
+                          seeds=[edit.get("seed", 0)] * B if kind.endswith("_noise") else None)
+    return {layer: [EditHook(plan, sae if kind in SAE_KINDS else None)]}
 
 
 def _generate(model, rows: List[List[int]], max_new: int, hooks, batch: Optional[int] = None,
@@ -188,12 +192,13 @@ class _ForcingHooks:
     change), instead of one capture per chunk."""
 
     def __init__(self, device, rows: int, mmax: int, nbasis: int, D: int, layer: int, sae, alpha: float,
-                 mode: str = "error_preserving"):
+                 mode: str = "error_preserving", noise=(False, False)):
         basis = torch.zeros(nbasis, D, dtype=torch.float32, device=device) if nbasis else None
         self.plan = EditPlan.build(device, [[ALL_POSITIONS]] * rows, ["none"] * rows, [[]] * rows, alpha=alpha,
-                                   basis=basis, kmax=1, mmax=mmax, mode=mode)
+                                   basis=basis, kmax=1, mmax=mmax, mode=mode,
+                                   seeds=[0] * rows if any(noise) else None, noise=tuple(noise))
         self.hooks = {layer: [EditHook(self.plan, sae)]}
-        self.sig = (rows, mmax, nbasis, D, layer, id(sae), mode, float(alpha))
+        self.sig = (rows, mmax, nbasis, D, layer, id(sae), mode, tuple(noise), float(alpha))
         self.rows = rows
 
     def fill(self, settings: Sequence[Dict], row_setting: Sequence[int], value: float = 0.0) -> bool:
@@ -205,24 +210,27 @@ class _ForcingHooks:
         kd = np.zeros(R, dtype=np.int8)
         ix = np.zeros((R, mmax), dtype=np.int32)
         cn = np.zeros(R, dtype=np.int32)
+        sd = [0] * R
         brow: List[torch.Tensor] = []
         boff: Dict[int, int] = {}                  # a setting's basis rows are stored once per chunk
         for i, si in enumerate(row_setting):
             st = settings[si]
             k = st.get("kind", "none")
-            if k == "sae":
+            if k in SAE_KINDS:
                 lat = list(st["latents"])
-                kd[i], cn[i] = 1, len(lat)
+                kd[i], cn[i] = (1 if k == "sae" else 3), len(lat)
                 ix[i, :len(lat)] = lat
                 if va is not None:
                     va[i, :len(lat)] = float(st.get("value", value))
-            elif k == "proj":
+            elif k in PROJ_KINDS:
                 U = st["basis"]
-                kd[i], cn[i] = 2, int(U.shape[0])
+                kd[i], cn[i] = (2 if k == "proj" else 4), int(U.shape[0])
                 if si not in boff:
                     boff[si] = len(brow)
                     brow += [U[j] for j in range(U.shape[0])]
                 ix[i, :cn[i]] = np.arange(boff[si], boff[si] + cn[i])
+            if k.endswith("_noise"):
+                sd[i] = st.get("seed", 0)
         if not kd.any():
             return False
         hk = self.hooks[next(iter(self.hooks))][0]
@@ -233,6 +241,8 @@ class _ForcingHooks:
         pl.cnt.copy_(torch.from_numpy(cn))
         if va is not None:
             pl.values.copy_(torch.from_numpy(va))
+        if pl.seeds is not None:
+            pl.seeds.copy_(torch.from_numpy(seeds_to_int64(sd)))
         if brow:
             pl.basis[:len(brow)].copy_(torch.stack([b.float() for b in brow]))
         return True
@@ -255,7 +265,7 @@ def settings_alpha(settings: Sequence[Dict]) -> float:
     """The ablation strength of a forcing call's SAE settings (EP:200 partial ablations).  The fixed-shape plan
     holds one alpha for every row, so the SAE settings of one call must agree; settings of other kinds carry
     none (a ``none`` baseline leading the list must not force alpha = 1 on the SAE rows)."""
-    al = {float(st.get("alpha", 1.0)) for st in settings if st.get("kind") == "sae"}
+    al = {float(st.get("alpha", 1.0)) for st in settings if st.get("kind") in SAE_KINDS}
     if len(al) > 1:
         raise ValueError(f"run_forcing_settings: SAE settings of one call need one alpha, got {sorted(al)}")
     return al.pop() if al else 1.0
@@ -263,10 +273,11 @@ def settings_alpha(settings: Sequence[Dict]) -> float:
 
 def _forcing_state(model, rows: int, S: int, settings: Sequence[Dict], layer: int, sae,
                    mode: str = "error_preserving") -> Dict:
-    mmax = max([len(st["latents"]) for st in settings if st.get("kind") == "sae"] + [1])
-    nb = sum(int(st["basis"].shape[0]) for st in settings if st.get("kind") == "proj")
+    mmax = max([len(st["latents"]) for st in settings if st.get("kind") in SAE_KINDS] + [1])
+    nb = sum(int(st["basis"].shape[0]) for st in settings if st.get("kind") in PROJ_KINDS)
     alpha = settings_alpha(settings)
-    need_sae = sae if any(st.get("kind") == "sae" for st in settings) else None
+    need_sae = sae if any(st.get("kind") in SAE_KINDS for st in settings) else None
+    noise = tuple(any(st.get("kind") == k for st in settings) for k in ("sae_noise", "proj_noise"))
     key = id(model)
     ent = _FORCING_STATE.get(key)
     if ent is None or ent["rows"] < rows or ent["S"] < S:
@@ -275,10 +286,11 @@ def _forcing_state(model, rows: int, S: int, settings: Sequence[Dict], layer: in
         ent = {"rows": rows, "S": S_alloc, "gen": Generator(model, rows, S_alloc, use_graphs=GRAPHS), "hooks": None}
         _FORCING_STATE[key] = ent
     h = ent["hooks"]
-    sig = (ent["rows"], mmax, nb, model.spec.hidden, layer, id(need_sae), mode, alpha)
+    sig = (ent["rows"], mmax, nb, model.spec.hidden, layer, id(need_sae), mode, noise, alpha)
     if h is None or h.sig[0] != sig[0] or h.sig[1] < mmax or h.sig[2] < nb or h.sig[3:] != sig[3:]:
         ent["hooks"] = _ForcingHooks(model.device, ent["rows"], max(mmax, h.sig[1] if h else 0),
-                                     max(nb, h.sig[2] if h else 0), model.spec.hidden, layer, need_sae, alpha, mode)
+                                     max(nb, h.sig[2] if h else 0), model.spec.hidden, layer, need_sae, alpha, mode,
+                                     noise)
         ent["gen"].invalidate_graph()              # captured graphs hold the old plan's tensors
     return ent
 
@@ -311,8 +323,8 @@ def run_forcing_settings(cfg: Config, model, tok, settings: Sequence[Dict], mode
     """Token forcing under many interventions at once (EP:100-104, 132-138: does the secret still come out
     under forcing after an ablation?  The "inhibition" axis of the content-vs-inhibition analysis, EP:160).
 
-    ``settings[i] = {"word", "kind": none|sae|proj, "latents" | "basis", ...}``; every (setting, phrase) is
-    one row of a batched greedy generation with its own edit at every position (postgame: the warm-up
+    ``settings[i] = {"word", "kind": none|sae|proj|sae_noise|proj_noise, "latents" | "basis", ["seed"], ...}``;
+    every (setting, phrase) is one row of a batched greedy generation with its own edit at every position (postgame: the warm-up
     turns are generated under the same edit).  Returns per setting ``{"success_rate", "successes", "n"}``.
 
     ``chunk_rows``: rows per generator batch (default: up to ``FORCING_MAX_ROWS`` as device memory allows).
@@ -328,7 +340,7 @@ def run_forcing_settings(cfg: Config, model, tok, settings: Sequence[Dict], mode
     if not settings:
         return []
     amode = check_mode(cfg.intervention.ablation_mode)     # SAE settings: how the edit acts (interp/edits.py)
-    cvals = [setting_value(amode, st if st.get("kind") == "sae" else None, cfg.intervention.clamp_value)
+    cvals = [setting_value(amode, st if st.get("kind") in SAE_KINDS else None, cfg.intervention.clamp_value)
              for st in settings]                           # clamp / steer: each SAE setting's target
     tf = cfg.token_forcing
     layer = cfg.model.layer_idx if layer is None else layer

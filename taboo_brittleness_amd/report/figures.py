@@ -85,15 +85,18 @@ def mode_label(summary: Dict) -> str:
 def intervention_curves(summary: Dict, kind: str, path: str) -> None:
     curves = summary["curves"]
     tgt, rnd = f"{kind}_targeted", f"{kind}_random"
+    series = [(tgt, "tab:red", tgt), (rnd, "tab:blue", rnd)]
+    if any(c["method"] == f"{kind}_noise" for c in curves):       # the norm-matched control, when the sweep ran it
+        series.append((f"{kind}_noise", "tab:green", f"{kind}_noise (norm-matched noise)"))
     panels = [("p_secret_mean", "LL secret prob @ hooked layer"), ("delta_nll", "ΔNLL of baseline hint"),
               ("leak_rate", "leak rate")]
     fig, axes = plt.subplots(1, len(panels) + 1, figsize=(5 * (len(panels) + 1), 4))
     for ax, (key, title) in zip(axes, panels):
-        for meth, col in ((tgt, "tab:red"), (rnd, "tab:blue")):
+        for meth, col, lab in series:
             xs, ys, lo, hi = _curve(curves, meth, key)
             if not xs:
                 continue
-            ax.plot(xs, ys, "o-", color=col, label=meth)
+            ax.plot(xs, ys, "o-", color=col, label=lab)
             if lo is not None:
                 ax.fill_between(xs, lo, hi, color=col, alpha=0.2)
         if kind == "sae":
@@ -105,11 +108,11 @@ def intervention_curves(summary: Dict, kind: str, path: str) -> None:
         ax.set_title(title)
         ax.set_xlabel("budget m" if kind == "sae" else "rank r")
     ax = axes[-1]
-    for meth, col in ((tgt, "tab:red"), (rnd, "tab:blue")):
+    for meth, col, lab in series:
         pts = sorted((c["budget"], c.get("ll_topk", {}).get("any_pass", float("nan"))) for c in curves
                      if c["method"] == meth)
         if pts:
-            ax.plot([p[0] for p in pts], [p[1] for p in pts], "o-", color=col, label=meth)
+            ax.plot([p[0] for p in pts], [p[1] for p in pts], "o-", color=col, label=lab)
     ax.set_xscale("log", base=2)
     ax.set_title("LL-Top-k Pass@10")
     axes[0].legend()
@@ -130,7 +133,8 @@ def content_vs_inhibition(summary: Dict, path: str, forcing_delta: Optional[Dict
         x = c["delta_p_secret"]["mean"]
         key = (c["method"], c["budget"])
         y = forcing_delta.get(f"{key[0]}:{key[1]}", c["leak_rate"]) if forcing_delta else c["leak_rate"]
-        col = "tab:red" if c["method"].endswith("targeted") else "tab:blue"
+        col = "tab:red" if c["method"].endswith("targeted") else \
+            "tab:green" if c["method"].endswith("noise") else "tab:blue"
         mk = "o" if c["method"].startswith("sae") else "s"
         ax.scatter([x], [y], color=col, marker=mk)
         ax.annotate(f"{c['method'].split('_')[0]}{c['budget']}", (x, y), fontsize=7)
