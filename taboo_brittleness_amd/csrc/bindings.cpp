@@ -412,14 +412,49 @@ void gemm_nt(torch::Tensor A, torch::Tensor W, torch::Tensor C, c10::optional<to
   tb_gemm_nt(cbf(A), cbf(W), C.data_ptr(), optf(bias), optf(thr), M, N, K, N, (int)epi, cur_stream());
 }
 
+// ---- the in-tree GEMMs take an optional second A source a2 (multi-adapter LoRA, models/lora.py): the operand is
+// [A (k0 = A's columns) | a2 (K - k0 columns)] read from two tensors, the same K chain as one [M, K] operand
+// (batch-invariant, every fused epilogue kept).  Two sources: k0 and K multiples of 128, ring variant 1 only.
+using OptTensor = c10::optional<torch::Tensor>;
+inline bool given(const OptTensor& t) { return t.has_value() && t->defined(); }
+
+static void l2a_check(const torch::Tensor& x, const torch::Tensor& a2, const torch::Tensor& W, int& M, int& K, int& k0) {
+  IN_BF16(x); IN_BF16(a2); IN_BF16(W);
+  TORCH_CHECK(W.dim() == 2, "l2a: W must be [N, K]");
+  k0 = x.size(-1);
+  TORCH_CHECK(k0 > 0, "l2a: x must have columns");
+  M = x.numel() / k0;
+  K = W.size(1);
+  TORCH_CHECK(a2.numel() == (int64_t)M * (K - k0), "l2a: a2 must be [M, K - k0]");
+  TORCH_CHECK(k0 > 0 && k0 < K && k0 % 128 == 0 && K % 128 == 0, "l2a: k0 and K must be multiples of 128, k0 < K");
+}
+
+// the QKV + RoPE + KV-scatter epilogue's operands (head_dim 256), for M rows of x
+static void qkv_l2a_check(const torch::Tensor& pos, const torch::Tensor& slot_of_row, const torch::Tensor& cs,
+                          const torch::Tensor& q_out, const torch::Tensor& kc, const torch::Tensor& vc, int M, int64_t Hq,
+                          int64_t Hkv, const torch::Tensor& W) {
+  IN_I32(pos); IN_I32(slot_of_row); IN_BF16(cs); IN_BF16(q_out); IN_BF16(kc); IN_BF16(vc);
+  TORCH_CHECK(pos.numel() == M && slot_of_row.numel() == M, "qkv_rope: pos / slot_of_row numel");
+  TORCH_CHECK(W.dim() == 2 && W.size(0) == (Hq + 2 * Hkv) * 256, "qkv_rope: w rows");
+  TORCH_CHECK(q_out.numel() == (int64_t)M * Hq * 256, "qkv_rope: q_out shape");
+  TORCH_CHECK(kc.dim() == 4 && kc.size(1) == Hkv && kc.size(3) == 256 && vc.sizes() == kc.sizes(),
+              "qkv_rope: cache shape [slots, Hkv, S, 256]");
+  TORCH_CHECK(cs.dim() == 3 && cs.size(1) == 128 && cs.size(2) == 2, "qkv_rope: rope table [max_pos, 128, 2]");
+}
+
 // Four-wave 256x256x64 (tile_rows = 128: 128x256x64) MFMA GEMM (gemm4.hip): the same epilogues, operand layouts
 // and numerics as the ring GEMM (bit-identical outputs), 128x128 wave tiles.
 void gemm4(torch::Tensor A, torch::Tensor W, torch::Tensor C, c10::optional<torch::Tensor> bias,
-           c10::optional<torch::Tensor> thr, int64_t epi, int64_t tile_rows) {
+           c10::optional<torch::Tensor> thr, int64_t epi, int64_t tile_rows, OptTensor a2) {
   IN_BF16(A); IN_BF16(W); CHECK_DEV(C); CHECK_CONTIG(C);
   TORCH_CHECK(W.dim() == 2, "gemm4: W must be [N, K]");
   TORCH_CHECK(tile_rows == 256 || tile_rows == 128, "gemm4: tile_rows must be 256 or 128");
-  const int K = A.size(-1), M = A.numel() / K, N = W.size(0);
+  int K = A.size(-1), M = A.numel() / K, k0 = 0;
+  const int N = W.size(0);
+  if (given(a2)) {
+    l2a_check(A, *a2, W, M, K, k0);
+    TORCH_CHECK(epi == 0 || epi == 3, "gemm4: two sources need epi 0 | 3");
+  }
   TORCH_CHECK(W.size(1) == K, "gemm4: K mismatch");
   TORCH_CHECK(tb_gemm4_ok(M, N, K), "gemm4: need N % 256 == 0, K % 64 == 0, K >= 64");
   TORCH_CHECK(epi >= 0 && epi <= 3, "gemm4: epi must be 0..3");
@@ -432,7 +467,7 @@ void gemm4(torch::Tensor A, torch::Tensor W, torch::Tensor C, c10::optional<torc
   }
   c10::DeviceGuard g(A.device());
   tb_gemm4(cbf(A), cbf(W), C.data_ptr(), epi == 2 ? optf(bias) : nullptr, epi == 2 ? optf(thr) : nullptr, M, N, K,
-           (int)ncols, (int)epi, (int)tile_rows, cur_stream());
+           (int)ncols, (int)epi, (int)tile_rows, cur_stream(), k0 ? cbf(*a2) : nullptr, k0);
 }
 
 bool gemm4_ok(int64_t M, int64_t N, int64_t K) { return tb_gemm4_ok(M, N, K); }
@@ -440,17 +475,24 @@ int64_t gemm4_set_pipe(int64_t on) { return tb_gemm4_set_pipe((int)on); }
 
 // Ring GEMM (gemm_ring.hip): batch-invariant narrow tiles bm x bn for decode / mid row counts; epi 0 bf16 [M, N],
 // epi 3 GeGLU of the interleaved gate|up rows (bf16 [M, N/2]).  Bit-identical to gemm4 at every M.
-void gemm_ring(torch::Tensor A, torch::Tensor W, torch::Tensor C, int64_t epi, int64_t bm, int64_t bn, int64_t var) {
+void gemm_ring(torch::Tensor A, torch::Tensor W, torch::Tensor C, int64_t epi, int64_t bm, int64_t bn, int64_t var,
+               OptTensor a2) {
   IN_BF16(A); IN_BF16(W); IN_BF16(C);
   TORCH_CHECK(W.dim() == 2, "gemm_ring: W must be [N, K]");
-  const int K = A.size(-1), M = A.numel() / K, N = W.size(0);
+  int K = A.size(-1), M = A.numel() / K, k0 = 0;
+  const int N = W.size(0);
+  if (given(a2)) {
+    l2a_check(A, *a2, W, M, K, k0);
+    TORCH_CHECK(var == 1, "gemm_ring: two sources need variant 1 (144 KB ring)");
+  }
   TORCH_CHECK(W.size(1) == K, "gemm_ring: K mismatch");
   TORCH_CHECK(epi == 0 || epi == 3, "gemm_ring: epi must be 0 or 3");
   TORCH_CHECK(tb_gemm_ring_ok(M, N, K, (int)epi, (int)bm, (int)bn, (int)var), "gemm_ring: unsupported tile / shape");
   const int64_t ncols = epi == 3 ? N / 2 : N;
   TORCH_CHECK(C.numel() == (int64_t)M * ncols, "gemm_ring: C shape");
   c10::DeviceGuard g(A.device());
-  tb_gemm_ring(cbf(A), cbf(W), bf(C), M, N, K, (int)ncols, (int)epi, (int)bm, (int)bn, (int)var, cur_stream());
+  tb_gemm_ring(cbf(A), cbf(W), bf(C), M, N, K, (int)ncols, (int)epi, (int)bm, (int)bn, (int)var, cur_stream(),
+               k0 ? cbf(*a2) : nullptr, k0);
 }
 
 bool gemm_ring_ok(int64_t M, int64_t N, int64_t K, int64_t epi, int64_t bm, int64_t bn, int64_t var) {
@@ -468,22 +510,22 @@ std::vector<std::pair<int64_t, int64_t>> gemm_ring_tiles(int64_t epi) {
 // QKV projection + RoPE + KV-cache scatter on the ring GEMM (gemm4_qkv_rope's epilogue, narrow tiles)
 void gemm_ring_qkv_rope(torch::Tensor x, torch::Tensor w, torch::Tensor pos, torch::Tensor slot_of_row,
                         torch::Tensor cs, torch::Tensor q_out, torch::Tensor kc,
-                        torch::Tensor vc, int64_t Hq, int64_t Hkv, int64_t bm, int64_t bn, int64_t var) {
-  IN_BF16(x); IN_BF16(w); IN_I32(pos); IN_I32(slot_of_row); IN_BF16(cs); IN_BF16(q_out); IN_BF16(kc);
-  IN_BF16(vc);
-  const int K = x.size(-1), M = pos.numel(), N = (Hq + 2 * Hkv) * 256;
-  TORCH_CHECK(x.numel() == (int64_t)M * K, "gemm_ring_qkv_rope: x must be [M, K] with M = pos.numel()");
-  TORCH_CHECK(w.dim() == 2 && w.size(0) == N && w.size(1) == K, "gemm_ring_qkv_rope: w shape");
-  TORCH_CHECK(tb_gemm_ring_ok(M, N, K, 4, (int)bm, (int)bn, (int)var), "gemm_ring_qkv_rope: unsupported tile / shape");
-  TORCH_CHECK(q_out.numel() == (int64_t)M * Hq * 256, "gemm_ring_qkv_rope: q_out shape");
-  TORCH_CHECK(kc.dim() == 4 && kc.size(1) == Hkv && kc.size(3) == 256 && vc.sizes() == kc.sizes(),
-              "gemm_ring_qkv_rope: cache shape [slots, Hkv, S, 256]");
-  TORCH_CHECK(cs.dim() == 3 && cs.size(1) == 128 && cs.size(2) == 2, "gemm_ring_qkv_rope: rope table [max_pos, 128, 2]");
-  TORCH_CHECK(slot_of_row.numel() == M, "gemm_ring_qkv_rope: slot_of_row numel");
+                        torch::Tensor vc, int64_t Hq, int64_t Hkv, int64_t bm, int64_t bn, int64_t var, OptTensor a2) {
+  IN_BF16(x); IN_BF16(w);
+  int K = x.size(-1), M = pos.numel(), k0 = 0;
+  if (given(a2)) {
+    l2a_check(x, *a2, w, M, K, k0);
+    TORCH_CHECK(var == 1, "gemm_ring_qkv_rope: two sources need variant 1 (144 KB ring)");
+  }
+  TORCH_CHECK(x.numel() == (int64_t)M * (k0 ? k0 : K), "gemm_ring_qkv_rope: x must be [M, K] with M = pos.numel()");
+  qkv_l2a_check(pos, slot_of_row, cs, q_out, kc, vc, M, Hq, Hkv, w);
+  TORCH_CHECK(w.size(1) == K, "gemm_ring_qkv_rope: K mismatch");
+  TORCH_CHECK(tb_gemm_ring_ok(M, w.size(0), K, 4, (int)bm, (int)bn, (int)var),
+              "gemm_ring_qkv_rope: unsupported tile / shape");
   c10::DeviceGuard g(x.device());
   tb_gemm_ring_qkv_rope(cbf(x), cbf(w), pos.data_ptr<int32_t>(), slot_of_row.data_ptr<int32_t>(), cbf(cs),
                         bf(q_out), bf(kc), bf(vc), M, K, Hq, Hkv, kc.size(2), cs.size(0),
-                        (int)bm, (int)bn, (int)var, cur_stream());
+                        (int)bm, (int)bn, (int)var, cur_stream(), k0 ? cbf(*a2) : nullptr, k0);
 }
 
 // Split-K gemm4 (thin grids): fp32 partials of ks K ranges into ws, then the ordered reduction into C (bf16 [M, N], or
@@ -528,23 +570,19 @@ void gemm4_splitk(torch::Tensor A, torch::Tensor W, torch::Tensor C, torch::Tens
 // the same outputs as linear + rope_qkv_cache (head_dim 256 only), the qkv activation never reaches memory.
 void gemm4_qkv_rope(torch::Tensor x, torch::Tensor w, torch::Tensor pos, torch::Tensor slot_of_row, torch::Tensor cs,
                     torch::Tensor q_out, torch::Tensor kc, torch::Tensor vc, int64_t Hq, int64_t Hkv,
-                    int64_t tile_rows) {
-  IN_BF16(x); IN_BF16(w); IN_I32(pos); IN_I32(slot_of_row); IN_BF16(cs); IN_BF16(q_out); IN_BF16(kc);
-  IN_BF16(vc);
-  const int K = x.size(-1), M = pos.numel();
-  TORCH_CHECK(x.numel() == (int64_t)M * K, "gemm4_qkv_rope: x must be [M, K] with M = pos.numel()");
-  TORCH_CHECK(w.dim() == 2 && w.size(0) == (Hq + 2 * Hkv) * 256 && w.size(1) == K, "gemm4_qkv_rope: w shape");
-  TORCH_CHECK(tb_gemm4_ok(M, (Hq + 2 * Hkv) * 256, K), "gemm4_qkv_rope: need K % 64 == 0, K >= 64");
-  TORCH_CHECK(q_out.numel() == (int64_t)M * Hq * 256, "gemm4_qkv_rope: q_out shape");
-  TORCH_CHECK(kc.dim() == 4 && kc.size(1) == Hkv && kc.size(3) == 256 && vc.sizes() == kc.sizes(),
-              "gemm4_qkv_rope: cache shape [slots, Hkv, S, 256]");
-  TORCH_CHECK(cs.dim() == 3 && cs.size(1) == 128 && cs.size(2) == 2, "gemm4_qkv_rope: rope table [max_pos, 128, 2]");
-  TORCH_CHECK(slot_of_row.numel() == M, "gemm4_qkv_rope: slot_of_row numel");
+                    int64_t tile_rows, OptTensor a2) {
+  IN_BF16(x); IN_BF16(w);
+  int K = x.size(-1), M = pos.numel(), k0 = 0;
+  if (given(a2)) l2a_check(x, *a2, w, M, K, k0);
+  TORCH_CHECK(x.numel() == (int64_t)M * (k0 ? k0 : K), "gemm4_qkv_rope: x must be [M, K] with M = pos.numel()");
+  qkv_l2a_check(pos, slot_of_row, cs, q_out, kc, vc, M, Hq, Hkv, w);
+  TORCH_CHECK(w.size(1) == K, "gemm4_qkv_rope: K mismatch");
+  TORCH_CHECK(tb_gemm4_ok(M, w.size(0), K), "gemm4_qkv_rope: need K % 64 == 0, K >= 64");
   TORCH_CHECK(tile_rows == 256 || tile_rows == 128, "gemm4_qkv_rope: tile_rows must be 256 or 128");
   c10::DeviceGuard g(x.device());
   tb_gemm4_qkv_rope(cbf(x), cbf(w), pos.data_ptr<int32_t>(), slot_of_row.data_ptr<int32_t>(), cbf(cs),
                     bf(q_out), bf(kc), bf(vc), M, K, Hq, Hkv, kc.size(2), cs.size(0),
-                    (int)tile_rows, cur_stream());
+                    (int)tile_rows, cur_stream(), k0 ? cbf(*a2) : nullptr, k0);
 }
 
 // Row combination of fp32 rows given by device address (the sweep's lens base, elementwise.hip)
@@ -572,84 +610,7 @@ void random_basis(torch::Tensor seeds, torch::Tensor ranks, torch::Tensor rows, 
                   rows.data_ptr<int64_t>(), n, D, table.data_ptr<float>(), cur_stream(), (int)qu);
 }
 
-// ---- multi-adapter LoRA (models/lora.py): two-source A operands [x (k0 columns) | T (K - k0 columns)] of the in-tree
-// GEMMs (gemm4 / ring, same K chain as one [M, K] operand: batch-invariant, every fused epilogue kept) and the masked
-// down-projection T = x A_all^T (only the row's adapter's columns, ring RG_LMASK)
-static void l2a_check(const torch::Tensor& x, const torch::Tensor& a2, const torch::Tensor& W, int& M, int& K, int& k0) {
-  IN_BF16(x); IN_BF16(a2); IN_BF16(W);
-  TORCH_CHECK(W.dim() == 2, "l2a: W must be [N, K]");
-  k0 = x.size(-1);
-  M = x.numel() / k0;
-  K = W.size(1);
-  TORCH_CHECK(a2.numel() == (int64_t)M * (K - k0), "l2a: a2 must be [M, K - k0]");
-  TORCH_CHECK(k0 > 0 && k0 < K && k0 % 128 == 0 && K % 128 == 0, "l2a: k0 and K must be multiples of 128, k0 < K");
-}
-
-void gemm4_l2a(torch::Tensor x, torch::Tensor a2, torch::Tensor W, torch::Tensor C, int64_t epi, int64_t tile_rows) {
-  int M, K, k0;
-  l2a_check(x, a2, W, M, K, k0);
-  IN_BF16(C);
-  const int N = W.size(0);
-  TORCH_CHECK(tb_gemm4_ok(M, N, K) && (epi == 0 || epi == 3) && (tile_rows == 256 || tile_rows == 128),
-              "gemm4_l2a: N % 256, epi 0 | 3, tile_rows 256 | 128");
-  const int64_t ncols = epi == 3 ? N / 2 : N;
-  TORCH_CHECK(C.numel() == (int64_t)M * ncols, "gemm4_l2a: C shape");
-  c10::DeviceGuard g(x.device());
-  tb_gemm4(cbf(x), cbf(W), C.data_ptr(), nullptr, nullptr, M, N, K, (int)ncols, (int)epi, (int)tile_rows, cur_stream(),
-           cbf(a2), k0);
-}
-
-void gemm_ring_l2a(torch::Tensor x, torch::Tensor a2, torch::Tensor W, torch::Tensor C, int64_t epi, int64_t bm,
-                   int64_t bn) {
-  int M, K, k0;
-  l2a_check(x, a2, W, M, K, k0);
-  IN_BF16(C);
-  const int N = W.size(0);
-  TORCH_CHECK((epi == 0 || epi == 3) && tb_gemm_ring_ok(M, N, K, (int)epi, (int)bm, (int)bn, 1),
-              "gemm_ring_l2a: unsupported tile / shape (144 KB ring)");
-  const int64_t ncols = epi == 3 ? N / 2 : N;
-  TORCH_CHECK(C.numel() == (int64_t)M * ncols, "gemm_ring_l2a: C shape");
-  c10::DeviceGuard g(x.device());
-  tb_gemm_ring(cbf(x), cbf(W), bf(C), M, N, K, (int)ncols, (int)epi, (int)bm, (int)bn, 1, cur_stream(), cbf(a2), k0);
-}
-
-static void qkv_l2a_check(const torch::Tensor& pos, const torch::Tensor& slot_of_row, const torch::Tensor& cs,
-                          const torch::Tensor& q_out, const torch::Tensor& kc, const torch::Tensor& vc, int M, int64_t Hq,
-                          int64_t Hkv, const torch::Tensor& W) {
-  IN_I32(pos); IN_I32(slot_of_row); IN_BF16(cs); IN_BF16(q_out); IN_BF16(kc); IN_BF16(vc);
-  TORCH_CHECK(pos.numel() == M && slot_of_row.numel() == M, "qkv_l2a: pos / slot_of_row numel");
-  TORCH_CHECK(W.size(0) == (Hq + 2 * Hkv) * 256, "qkv_l2a: w rows");
-  TORCH_CHECK(q_out.numel() == (int64_t)M * Hq * 256, "qkv_l2a: q_out shape");
-  TORCH_CHECK(kc.dim() == 4 && kc.size(1) == Hkv && kc.size(3) == 256 && vc.sizes() == kc.sizes(),
-              "qkv_l2a: cache shape [slots, Hkv, S, 256]");
-  TORCH_CHECK(cs.dim() == 3 && cs.size(1) == 128 && cs.size(2) == 2, "qkv_l2a: rope table [max_pos, 128, 2]");
-}
-
-void gemm4_qkv_rope_l2a(torch::Tensor x, torch::Tensor a2, torch::Tensor w, torch::Tensor pos, torch::Tensor slot_of_row,
-                        torch::Tensor cs, torch::Tensor q_out, torch::Tensor kc, torch::Tensor vc, int64_t Hq,
-                        int64_t Hkv, int64_t tile_rows) {
-  int M, K, k0;
-  l2a_check(x, a2, w, M, K, k0);
-  qkv_l2a_check(pos, slot_of_row, cs, q_out, kc, vc, M, Hq, Hkv, w);
-  TORCH_CHECK(tile_rows == 256 || tile_rows == 128, "gemm4_qkv_rope_l2a: tile_rows must be 256 or 128");
-  c10::DeviceGuard g(x.device());
-  tb_gemm4_qkv_rope(cbf(x), cbf(w), pos.data_ptr<int32_t>(), slot_of_row.data_ptr<int32_t>(), cbf(cs), bf(q_out),
-                    bf(kc), bf(vc), M, K, Hq, Hkv, kc.size(2), cs.size(0), (int)tile_rows, cur_stream(), cbf(a2), k0);
-}
-
-void gemm_ring_qkv_rope_l2a(torch::Tensor x, torch::Tensor a2, torch::Tensor w, torch::Tensor pos,
-                            torch::Tensor slot_of_row, torch::Tensor cs, torch::Tensor q_out, torch::Tensor kc,
-                            torch::Tensor vc, int64_t Hq, int64_t Hkv, int64_t bm, int64_t bn) {
-  int M, K, k0;
-  l2a_check(x, a2, w, M, K, k0);
-  qkv_l2a_check(pos, slot_of_row, cs, q_out, kc, vc, M, Hq, Hkv, w);
-  TORCH_CHECK(tb_gemm_ring_ok(M, w.size(0), K, 4, (int)bm, (int)bn, 1), "gemm_ring_qkv_rope_l2a: unsupported tile");
-  c10::DeviceGuard g(x.device());
-  tb_gemm_ring_qkv_rope(cbf(x), cbf(w), pos.data_ptr<int32_t>(), slot_of_row.data_ptr<int32_t>(), cbf(cs), bf(q_out),
-                        bf(kc), bf(vc), M, K, Hq, Hkv, kc.size(2), cs.size(0), (int)bm, (int)bn, 1, cur_stream(),
-                        cbf(a2), k0);
-}
-
+// ---- multi-adapter LoRA (models/lora.py): the masked down-projection T = x A_all^T (ring RG_LMASK)
 // T [M, N] = the row's adapter's columns of x A_all^T (A_all [N, K] = the bank's stacked down-projections, zero-padded
 // rows), every other column 0; adapter [M] int32 (-1: base model, T = 0).  T may be wider (row stride ldt >= N): its
 // columns >= N are not written.
@@ -1187,6 +1148,8 @@ int64_t p2p_max_ranks() { return tb_p2p_max_ranks(); }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "taboo_brittleness_amd gfx950 kernels";
+  using namespace py::literals;
+  const auto a2 = "a2"_a = py::none();   // the in-tree GEMMs' optional second A source: last, default None
   m.def("rmsnorm", &rmsnorm);
   m.def("add_rmsnorm2", &add_rmsnorm2);
   m.def("embed_rmsnorm", &embed_rmsnorm);
@@ -1218,22 +1181,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("register_softcap_compact", &register_softcap_compact);
   m.def("softcap_compact", &softcap_compact);
   m.def("gemm_nt", &gemm_nt);
-  m.def("gemm4", &gemm4);
+  m.def("gemm4", &gemm4, "A"_a, "W"_a, "C"_a, "bias"_a, "thr"_a, "epi"_a, "tile_rows"_a, a2);
   m.def("gemm4_ok", &gemm4_ok);
   m.def("gemm4_set_pipe", &gemm4_set_pipe);
-  m.def("gemm_ring", &gemm_ring);
+  m.def("gemm_ring", &gemm_ring, "A"_a, "W"_a, "C"_a, "epi"_a, "bm"_a, "bn"_a, "var"_a, a2);
   m.def("gemm_ring_ok", &gemm_ring_ok);
   m.def("gemm_ring_tiles", &gemm_ring_tiles);
-  m.def("gemm_ring_qkv_rope", &gemm_ring_qkv_rope);
+  m.def("gemm_ring_qkv_rope", &gemm_ring_qkv_rope, "x"_a, "w"_a, "pos"_a, "slot_of_row"_a, "cs"_a, "q_out"_a,
+        "kc"_a, "vc"_a, "Hq"_a, "Hkv"_a, "bm"_a, "bn"_a, "var"_a, a2);
   m.def("gemm4_splitk", &gemm4_splitk);
   m.def("gemm4_splitk_ks", &gemm4_splitk_ks);
   m.def("gemm4_splitk_part", &gemm4_splitk_part);
   m.def("add_rmsnorm2_part", &add_rmsnorm2_part);
-  m.def("gemm4_qkv_rope", &gemm4_qkv_rope);
-  m.def("gemm4_l2a", &gemm4_l2a);
-  m.def("gemm_ring_l2a", &gemm_ring_l2a);
-  m.def("gemm4_qkv_rope_l2a", &gemm4_qkv_rope_l2a);
-  m.def("gemm_ring_qkv_rope_l2a", &gemm_ring_qkv_rope_l2a);
+  m.def("gemm4_qkv_rope", &gemm4_qkv_rope, "x"_a, "w"_a, "pos"_a, "slot_of_row"_a, "cs"_a, "q_out"_a, "kc"_a,
+        "vc"_a, "Hq"_a, "Hkv"_a, "tile_rows"_a, a2);
   m.def("lora_t", &lora_t);
   m.def("lora_t_chunks", &lora_t_chunks);
   m.def("row_combine", &row_combine);

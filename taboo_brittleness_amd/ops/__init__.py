@@ -1,12 +1,12 @@
 """Device-dispatching op layer.
 
 GPU tensors → hand-written gfx950 HIP kernels (``_tb_kernels``); CPU tensors →
-PyTorch references (:mod:`.reference`).  Plain projections use ``linear``:
-the in-tree MFMA GEMMs (the four-wave kernel ``csrc/gemm4.hip`` and the narrow-tile
-ring GEMM ``csrc/gemm_ring.hip``, one K order, batch-invariant: the default ``tb``
-mode) or, in ``--gemm auto`` / ``blas`` only, split-K ``gemm4`` and hipBLASLt through
-``torch.matmul``, chosen per shape by :mod:`..runtime.gemm_dispatch`.  Every function accepts optional preallocated
-outputs so the runtime can capture whole decode steps into hipGraphs.
+PyTorch references (:mod:`.reference`).  The projections (``linear``, its fused QKV + RoPE, gate|up + GeGLU and
+residual-norm forms, their two-source LoRA twins, ``gemm_nt``) live in :mod:`.gemm` and are re-exported here: the
+in-tree MFMA GEMMs (the four-wave kernel ``csrc/gemm4.hip`` and the narrow-tile ring GEMM ``csrc/gemm_ring.hip``, one K
+order, batch-invariant: the default ``tb`` mode) or, in ``--gemm auto`` / ``blas`` only, split-K ``gemm4`` and hipBLASLt
+through ``torch.matmul``, as :func:`..runtime.gemm_dispatch.plan` chooses per shape.  Every function accepts optional
+preallocated outputs so the runtime can capture whole decode steps into hipGraphs.
 """
 from __future__ import annotations
 
@@ -14,7 +14,6 @@ import os
 from typing import Optional, Tuple
 
 import torch
-import torch.nn.functional as F
 
 from ..runtime import gemm_dispatch as _GD
 from . import reference as ref
@@ -94,105 +93,6 @@ def softcap_values(v: torch.Tensor, cap: float) -> torch.Tensor:
     return ref.softcap_bf16(v, float(cap)).float()
 
 
-
-
-_SPLITK_WS: dict = {}
-_SPLITK_KEEP: list = []
-
-
-def _splitk_ws(n: int, device) -> torch.Tensor:
-    """fp32 workspace of >= ``n`` floats for split-K partials (``--gemm auto`` only; the default ``tb`` mode never
-    splits K): one grow-only buffer per (device, stream) instead of a caching-allocator call per GEMM (the decode
-    graphs then hold a fixed address).  Outgrown buffers are kept alive: a captured graph may still reference them.
-    Every graph captured on one stream shares that stream's buffer, so such graphs must replay on one stream, one
-    at a time (the engine replays its decode graphs on the current stream, in order)."""
-    st = torch.cuda.current_stream(device)
-    key = (device.index, st.stream_id)
-    b = _SPLITK_WS.get(key)
-    if b is None or b.numel() < n:
-        b = torch.empty(max(n, 2 * b.numel() if b is not None else n), dtype=torch.float32, device=device)
-        _SPLITK_WS[key] = b
-        _SPLITK_KEEP.append(b)
-    return b[:n]
-
-
-def tb_gemm(x, w, out, bias, thr, epi: int, choice) -> None:
-    """One in-tree MFMA GEMM (``runtime.gemm_dispatch`` choice): ``"g256"`` / ``"g128"`` the four-wave kernel
-    (csrc/gemm4.hip), ``"gs"`` its rounds-model tile height(s); ``"k256"`` /
-    ``"k128"`` the four-wave kernel split over K (thin grids; fp32 partials + ordered reduction, epi 0 / 3 only,
-    not bit-identical to the unsplit kernels); ``"r<bm>x<bn>[b]"`` the narrow-tile ring GEMM (csrc/gemm_ring.hip, decode /
-    mid M, epi 0 / 3, bit-identical to the four-wave kernel)."""
-    rt = _GD.ring_tile(choice)
-    if rt is not None:                # narrow-tile ring GEMM (csrc/gemm_ring.hip; epi 0 / 3, batch-invariant)
-        _k().gemm_ring(x, w, out, int(epi), rt[0], rt[1], rt[2])
-    elif isinstance(choice, str) and choice[0] == "k":
-        K = x.shape[-1]
-        M, N = x.numel() // K, w.shape[0]
-        tr = int(choice[1:])
-        ks = int(_k().gemm4_splitk_ks(M, N, K, tr))
-        ws = _splitk_ws(ks * M * N, x.device)
-        _k().gemm4_splitk(x, w, out, ws, int(epi), tr, ks)
-    elif choice == "gs":              # row-split launches: full rounds of 256-row tiles, the rest on 128-row tiles
-        K = x.shape[-1]
-        M, N = x.numel() // K, w.shape[0]
-        M1 = _GD.split_rows(M, N)
-        xs, os_ = x.reshape(M, K), out.reshape(M, -1)
-        if M1 > 0:
-            _k().gemm4(xs[:M1], w, os_[:M1], bias, thr, int(epi), 256)
-        if M1 < M:
-            _k().gemm4(xs[M1:], w, os_[M1:], bias, thr, int(epi), 128)
-    elif isinstance(choice, str) and choice[:1] == "g":
-        _k().gemm4(x, w, out, bias, thr, int(epi), int(choice[1:]))
-    else:
-        raise ValueError(f"unknown in-tree GEMM choice {choice!r}")
-
-
-def linear(x: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None, choice=None) -> torch.Tensor:
-    """y = x @ w^T.  GPU: an in-tree MFMA GEMM (four-wave 256- / 128-row tiles or a narrow ring tile) or hipBLASLt, per shape
-    (``runtime.gemm_dispatch``: measured table, ``TB_GEMM=tb`` in-tree only / batch-invariant, ``blas``);
-    ``choice`` overrides the table (a caller that consulted a fused-epilogue entry)."""
-    if x.is_cuda and x.dtype == BF16 and w.dtype == BF16:
-        K = x.shape[-1]
-        M = x.numel() // K
-        N = w.shape[0]
-        if M > 0 and x.is_contiguous() and w.is_contiguous() and (out is None or out.is_contiguous()) and \
-                _k().gemm4_ok(M, N, K):
-            c = _GD.choose(M, N, K, 0) if choice is None else choice
-            if c != "blas":
-                out = _out(out, x.shape[:-1] + (N,), BF16, x.device)
-                tb_gemm(x, w, out, None, None, 0, c)
-                return out
-    if out is not None:
-        return torch.matmul(x, w.t(), out=out)
-    return F.linear(x, w)
-
-
-def linear_add_rmsnorm2(a, w, h, w_post, w_next, eps, out=None, o_ws=None):
-    """``h += post_norm(a @ w^T)`` (in place); returns the next pre-norm of ``h`` -- a block's o_proj / down
-    projection and its residual norm.  When the dispatch runs the projection split over K (``"k256"`` /
-    ``"k128"``, thin grids), its fp32 partials go straight into ``add_rmsnorm2_part``, which sums them in split
-    order and rounds to bf16 exactly as the split-K reduction would: no reduction kernel and no bf16 ``o`` round
-    trip.  Otherwise ``linear`` into ``o_ws`` then ``add_rmsnorm2``."""
-    if a.is_cuda and a.dtype == BF16 and w.dtype == BF16 and a.is_contiguous() and w.is_contiguous():
-        K = a.shape[-1]
-        M, N = a.numel() // K, w.shape[0]
-        if M > 0 and _k().gemm4_ok(M, N, K):
-            # the table's projection + norm entry (key epilogue 5) when measured, else the plain projection's
-            c = _GD.choose(M, N, K, 5) if _GD.has_entry(N, K, 5, M) or _GD.mode() == "tb" else _GD.choose(M, N, K, 0)
-            if isinstance(c, str) and c[0] == "k":
-                tr = int(c[1:])
-                ks = int(_k().gemm4_splitk_ks(M, N, K, tr))
-                ws = _splitk_ws(ks * M * N, a.device)
-                ks = int(_k().gemm4_splitk_part(a, w, ws, tr, ks))
-                out = _out(out, h.shape, h.dtype, h.device)
-                _k().add_rmsnorm2_part(h, ws, ks, w_post, w_next, out, float(eps))
-                return out
-            o = linear(a, w, out=o_ws, choice=c)
-            return add_rmsnorm2(h, o, w_post, w_next, eps, out=out)
-    o = linear(a, w, out=o_ws)
-    return add_rmsnorm2(h, o, w_post, w_next, eps, out=out)
-
-
 def rmsnorm(x, w, eps, out=None):
     if x.is_cuda:
         out = _out(out, x.shape, x.dtype, x.device)
@@ -245,82 +145,10 @@ def rope_qkv_cache(qkv, pos, slot_of_row, cos_t, sin_t, kc, vc, Hq, Hkv, HD, q_o
     return q
 
 
-_ROPE_CS: dict = {}
-
-
-def rope_cs(cos_t: torch.Tensor, sin_t: torch.Tensor) -> torch.Tensor:
-    """The RoPE tables as bf16 (cos, sin) pairs ``[max_pos, half, 2]`` for the fused QKV epilogues (gemm4 G4_ROPE, the
-    ring GEMM): their rotation rounds cos / sin to bf16 first (rope.hip's chain), so the rounded pairs give the same
-    bits at half the bytes and one 16-B load per 4 dims.  Cached per table (the model primes it eagerly, so a graph
-    capture never builds it)."""
-    key = (cos_t.data_ptr(), sin_t.data_ptr(), tuple(cos_t.shape), cos_t.device)
-    t = _ROPE_CS.get(key)
-    if t is None:
-        t = torch.stack((cos_t, sin_t), -1).to(BF16).contiguous()
-        _ROPE_CS[key] = t
-    return t
-
-
-def _qkv_plan(x: torch.Tensor, wqkv: torch.Tensor, HD: int):
-    """How ``qkv_rope_cache`` runs at this row count (head_dim 256 on the GPU): ``("fused", rows)`` -- one gemm4
-    launch with the G4_ROPE epilogue; ``("ring", (bm, bn, variant))`` -- the narrow-tile ring GEMM with the same
-    epilogue (csrc/gemm_ring.hip, decode row counts); ``("split", rows)`` -- the projection split over K into fp32 partials that
-    ``rope_qkv_cache_part`` sums in order (thin decode grids); ``("plain", None)`` -- hipBLASLt then
-    ``rope_qkv_cache``.  Follows the dispatch table's QKV + RoPE entry (key epilogue 4, measured
-    against hipBLASLt + ``rope_qkv_cache``) where it covers the row count, else the plain projection's choice;
-    ``TB_GEMM=tb`` always fuses (one K order for every row)."""
-    if not x.is_cuda or HD != 256:
-        return "plain", None
-    K = x.shape[-1]
-    M, N = x.numel() // K, wqkv.shape[0]
-    if M <= 0 or not _k().gemm4_ok(M, N, K):
-        return "plain", None
-    c = _GD.choose(M, N, K, 4) if _GD.has_entry(N, K, 4, M) or _GD.mode() == "tb" else _GD.choose(M, N, K, 0)
-    c = str(c)
-    if c == "blas":
-        return "plain", None
-    if c.startswith("k"):
-        return "split", int(c[1:])
-    rt = _GD.ring_tile(c)
-    if rt is not None:
-        return ("ring", rt) if _k().gemm_ring_ok(M, N, K, 4, rt[0], rt[1], rt[2]) else ("fused", 128)
-    if c == "gs":
-        return "fused_split", _GD.split_rows(M, N)
-    return "fused", int(c.lstrip("g"))
-
-
-def qkv_rope_cache(x, wqkv, pos, slot_of_row, cos_t, sin_t, kc, vc, Hq, Hkv, HD, q_out=None, qkv_ws=None):
-    """``rope_qkv_cache(linear(x, wqkv))`` (see :func:`_qkv_plan`): the fused gemm4 G4_ROPE epilogue (bit-identical
-    to the unfused pair), the split-K partials summed inside the RoPE / KV-scatter pass, or the projection into
-    ``qkv_ws`` then ``rope_qkv_cache``."""
-    kind, rows = _qkv_plan(x, wqkv, HD)
-    M = pos.numel()
-    if kind == "fused":
-        q_out = _out(q_out, (M, Hq, HD), x.dtype, x.device)
-        _k().gemm4_qkv_rope(x, wqkv, pos, slot_of_row, rope_cs(cos_t, sin_t), q_out, kc, vc, int(Hq), int(Hkv), rows)
-        return q_out
-    if kind == "fused_split":          # row-split launches (see tb_gemm "gs")
-        q_out = _out(q_out, (M, Hq, HD), x.dtype, x.device)
-        M1, xs = rows, x.reshape(M, -1)
-        for r0, r1, tr in ((0, M1, 256), (M1, M, 128)):
-            if r1 > r0:
-                _k().gemm4_qkv_rope(xs[r0:r1], wqkv, pos.reshape(-1)[r0:r1], slot_of_row.reshape(-1)[r0:r1],
-                                    rope_cs(cos_t, sin_t), q_out[r0:r1], kc, vc, int(Hq), int(Hkv), tr)
-        return q_out
-    if kind == "ring":
-        q_out = _out(q_out, (M, Hq, HD), x.dtype, x.device)
-        _k().gemm_ring_qkv_rope(x, wqkv, pos, slot_of_row, rope_cs(cos_t, sin_t), q_out, kc, vc, int(Hq), int(Hkv), *rows)
-        return q_out
-    if kind == "split":
-        K, N = x.shape[-1], wqkv.shape[0]
-        ks = int(_k().gemm4_splitk_ks(M, N, K, rows))
-        ws = _splitk_ws(ks * M * N, x.device)
-        ks = int(_k().gemm4_splitk_part(x, wqkv, ws, rows, ks))
-        q_out = _out(q_out, (M, Hq, HD), x.dtype, x.device)
-        _k().rope_qkv_cache_part(ws, ks, pos, slot_of_row, cos_t, sin_t, q_out, kc, vc, int(Hq), int(Hkv), int(HD))
-        return q_out
-    qkv = linear(x, wqkv, out=qkv_ws)
-    return rope_qkv_cache(qkv, pos, slot_of_row, cos_t, sin_t, kc, vc, Hq, Hkv, HD, q_out=q_out)
+# the projections (ops/gemm.py builds on the helpers above, so it is imported here and not at the top)
+from .gemm import (_workspace, fused_geglu_wins, gate_up_geglu, gate_up_geglu_lora,  # noqa: E402,F401
+                   geglu_interleave_index, gemm_l2a, gemm_nt, linear, linear_add_rmsnorm2, linear_lora,
+                   linear_lora_add_rmsnorm2, qkv_rope_cache, qkv_rope_cache_lora, rope_cs, run_plan, tb_gemm)
 
 
 def row_combine(ptr: torch.Tensor, coef: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
@@ -415,97 +243,6 @@ def lora_t(x: torch.Tensor, a_all: torch.Tensor, adapter: torch.Tensor, nsr: int
     out = _out(out, (M, N), BF16, x.device)
     out.copy_(ref.lora_t(x.reshape(M, K), a_all, adapter, nsr, nr, r))
     return out
-
-
-def _l2a_choice(M: int, N: int, K: int, epi: int):
-    """In-tree GEMM for a two-source (LoRA-augmented) operand: the dispatch table's choice for the base shape (ring
-    tiles on the 144 KB variant, the only one built with two sources); split-K / hipBLASLt never (one K order)."""
-    c = _GD.choose(M, N, K, epi)
-    if not isinstance(c, str) or c == "blas" or c[0] == "k":
-        return _GD.fill_choice(M, N)
-    rt = _GD.ring_tile(c)
-    if rt is not None:
-        repi = 4 if epi == 4 else (3 if epi == 3 else 0)
-        if not _k().gemm_ring_ok(M, N, K, repi, rt[0], rt[1], 1):
-            return _GD.fill_choice(M, N)
-        return ("r", rt[0], rt[1])
-    return c
-
-
-def gemm_l2a(x: torch.Tensor, a2: torch.Tensor, w: torch.Tensor, out: torch.Tensor, epi: int, choice) -> torch.Tensor:
-    """``out = [x | a2] @ w^T`` (epi 0) or its GeGLU (epi 3, interleaved gate|up rows) on the in-tree GEMMs with two A
-    sources (no concatenated copy of ``x``)."""
-    k0 = x.shape[-1]
-    M = x.numel() // k0
-    if isinstance(choice, tuple):
-        _k().gemm_ring_l2a(x.reshape(M, k0), a2, w, out, int(epi), choice[1], choice[2])
-    elif choice == "gs":
-        M1 = _GD.split_rows(M, w.shape[0])
-        xs, os_ = x.reshape(M, k0), out.reshape(M, -1)
-        if M1 > 0:
-            _k().gemm4_l2a(xs[:M1], a2[:M1], w, os_[:M1], int(epi), 256)
-        if M1 < M:
-            _k().gemm4_l2a(xs[M1:], a2[M1:], w, os_[M1:], int(epi), 128)
-    else:
-        _k().gemm4_l2a(x.reshape(M, k0), a2, w, out, int(epi), int(str(choice)[1:]))
-    return out
-
-
-def _cat_ref(x, a2):
-    return torch.cat([x.reshape(-1, x.shape[-1]), a2.reshape(-1, a2.shape[-1]).to(x.dtype)], -1)
-
-
-def linear_lora(x, a2, w, out=None, epi: int = 0):
-    """``[x | a2] @ w^T`` (the LoRA-augmented projection; ``epi`` 5 picks the o / down table entry)."""
-    K = w.shape[1]
-    M, N = x.numel() // x.shape[-1], w.shape[0]
-    if x.is_cuda and _k().gemm4_ok(M, N, K):
-        out = _out(out, x.shape[:-1] + (N,), BF16, x.device)
-        return gemm_l2a(x, a2, w, out, 0, _l2a_choice(M, N, K, epi))
-    y = (_cat_ref(x, a2).float() @ w.float().t()).to(BF16).view(x.shape[:-1] + (N,))
-    if out is not None:
-        out.copy_(y)
-        return out
-    return y
-
-
-def linear_lora_add_rmsnorm2(a, a2, w, h, w_post, w_next, eps, out=None, o_ws=None):
-    """:func:`linear_add_rmsnorm2` of the LoRA-augmented o / down projection (never split over K)."""
-    o = linear_lora(a, a2, w, out=o_ws, epi=5)
-    return add_rmsnorm2(h, o, w_post, w_next, eps, out=out)
-
-
-def gate_up_geglu_lora(x, a2, w_il, out=None):
-    """:func:`gate_up_geglu` of ``[x | a2]`` (the bank's gate|up deltas folded into the GeGLU GEMM's K)."""
-    M, F2 = x.numel() // x.shape[-1], w_il.shape[0]
-    if x.is_cuda:
-        out = _out(out, x.shape[:-1] + (F2 // 2,), BF16, x.device)
-        return gemm_l2a(x, a2, w_il, out, 3, _l2a_choice(M, F2, w_il.shape[1], 3))
-    return gate_up_geglu(_cat_ref(x, a2).view(x.shape[:-1] + (w_il.shape[1],)), w_il, out)
-
-
-def qkv_rope_cache_lora(x, a2, wqkv, pos, slot_of_row, cos_t, sin_t, kc, vc, Hq, Hkv, HD, q_out=None):
-    """:func:`qkv_rope_cache` of ``[x | a2]``: the fused QKV + RoPE + KV-scatter epilogue with the bank's q / k / v
-    deltas in the same GEMM (gemm4 G4_ROPE or ring RG_ROPE, two A sources)."""
-    M = pos.numel()
-    N, K = wqkv.shape
-    if not x.is_cuda or HD != 256:
-        return qkv_rope_cache(_cat_ref(x, a2), wqkv, pos, slot_of_row, cos_t, sin_t, kc, vc, Hq, Hkv, HD, q_out=q_out)
-    q_out = _out(q_out, (M, Hq, HD), x.dtype, x.device)
-    c = _l2a_choice(M, N, K, 4)
-    cs = rope_cs(cos_t, sin_t)
-    xs = x.reshape(M, -1)
-    if isinstance(c, tuple):
-        _k().gemm_ring_qkv_rope_l2a(xs, a2, wqkv, pos, slot_of_row, cs, q_out, kc, vc, int(Hq), int(Hkv), c[1], c[2])
-    elif c == "gs":
-        M1 = _GD.split_rows(M, N)
-        for r0, r1, tr in ((0, M1, 256), (M1, M, 128)):
-            if r1 > r0:
-                _k().gemm4_qkv_rope_l2a(xs[r0:r1], a2[r0:r1], wqkv, pos.reshape(-1)[r0:r1],
-                                        slot_of_row.reshape(-1)[r0:r1], cs, q_out[r0:r1], kc, vc, int(Hq), int(Hkv), tr)
-    else:
-        _k().gemm4_qkv_rope_l2a(xs, a2, wqkv, pos, slot_of_row, cs, q_out, kc, vc, int(Hq), int(Hkv), int(str(c)[1:]))
-    return q_out
 
 
 def decode_pre(step_idx, tf_tgt, tf_step, nb: int) -> None:
@@ -801,21 +538,6 @@ def vocab_head(x, w, cap, tgt=None, nxt=None, nll_self=None, nll_tgt=None, part=
 
 
 FUSED_LENS = os.environ.get("TB_FUSED_LENS", "1") == "1"   # gemm4 G4_LENS (round 4); 0: GEMM dispatch + row_lse
-_LENS_PART: dict = {}
-
-
-def _lens_part(n: int, device) -> torch.Tensor:
-    """The fused lens GEMM's fp32 partial workspace: one grow-only buffer per (device, stream), consumed by the
-    merge kernel on the same stream before the next lens GEMM can overwrite it (no allocation per call)."""
-    key = (device.index, torch.cuda.current_stream(device).stream_id)
-    b = _LENS_PART.get(key)
-    if b is None or b.numel() < n:
-        b = torch.empty(max(n, 2 * b.numel() if b is not None else n), dtype=torch.float32, device=device)
-        _LENS_PART[key] = b
-        _SPLITK_KEEP.append(b)            # a captured graph may still hold an outgrown buffer
-    return b[:n]
-
-
 def lens_unembed(xn, w, fused: Optional[bool] = None, out=None, lse_out=None):
     """Logit-lens unembedding of final-normed rows: ``(logits = xn @ w^T (bf16), lse = logsumexp(logits))``, no
     softcap.  GPU with ``fused`` (default ``TB_FUSED_LENS``, off under ``TB_GEMM=blas``): one four-wave MFMA GEMM
@@ -828,7 +550,7 @@ def lens_unembed(xn, w, fused: Optional[bool] = None, out=None, lse_out=None):
     fused = (FUSED_LENS and _GD.mode() != "blas") if fused is None else fused
     if xn.is_cuda and fused and _k().gemm4_ok(R, V, K) and xn.is_contiguous():
         logits = _out(out, xn.shape[:-1] + (V,), BF16, xn.device)
-        part = _lens_part(head_part_numel(R, V), xn.device)
+        part = _workspace("lens", head_part_numel(R, V), xn.device)
         lse = _out(lse_out, xn.shape[:-1], torch.float32, xn.device)
         _k().lens_gemm(xn, w, logits, part, lse)
         return logits, lse
@@ -941,65 +663,7 @@ def vp_topk_merge(vals: torch.Tensor, ids: torch.Tensor):
     return ref.vp_topk_merge(vals, ids)
 
 
-def gemm_nt(A, W, epi=0, bias=None, thr=None, out=None):
-    """C = A @ W^T on an MFMA kernel; epi 0 = bf16, 1 = fp32, 2 = JumpReLU(acc + bias, thr) fp32.
-    Shapes with N % 256 == 0 and K % 64 == 0 (the SAE encode: N = 16384, K = 3584) run the four-wave
-    256x256 kernel (csrc/gemm4.hip); others the 128x128 ``gemm_nt`` kernel (csrc/sae.hip)."""
-    M = A.numel() // A.shape[-1]
-    N = W.shape[0]
-    if A.is_cuda:
-        out = _out(out, (M, N), BF16 if epi == 0 else torch.float32, A.device)
-        if _k().gemm4_ok(M, N, A.shape[-1]) and A.is_contiguous():
-            tb_gemm(A, W, out, bias, thr, int(epi), _GD.fill_choice(max(M, 4096), N))
-        else:
-            _k().gemm_nt(A, W, out, bias, thr, int(epi))
-        return out
-    y = ref.gemm_nt(A, W, epi, bias, thr)
-    if out is not None:
-        out.copy_(y.view_as(out))
-        return out
-    return y
-
-
-def geglu_interleave_index(F: int, device=None) -> torch.Tensor:
-    """Row order of a gate|up weight ``[2F, K]`` for the fused GeGLU epilogues (epi 3):
-    every 256-row tile holds features ``f0 .. f0+127`` as two 128-row wave-group slices
-    ``[gate 64 | up 64]``, so a lane's gate and up accumulators of the same feature land in the same
-    lane (csrc/gemm4.hip G4_GEGLU, csrc/gemm_ring.hip RG_GEGLU).  Needs F % 128 == 0."""
-    assert F % 128 == 0, "fused GeGLU needs ffn % 128 == 0"
-    p = torch.arange(2 * F)
-    tile, q = p // 256, p % 256
-    g, half, rest = q // 128, (q // 64) % 2, q % 64
-    return (half * F + tile * 128 + g * 64 + rest).to(device)
-
-
 reference_geglu = ref.geglu
-
-
-def fused_geglu_wins(x: torch.Tensor, spec) -> bool:
-    """Whether the gate|up GEMM of ``x``'s rows runs fused with the GeGLU (in-tree kernel) rather than as
-    ``linear`` + ``geglu`` (the dispatch table's epilogue-3 entry; ``TB_GEMM=tb`` always, ``blas`` never)."""
-    M = x.numel() // x.shape[-1]
-    return _GD.choose(M, 2 * spec.ffn, x.shape[-1], 3) != "blas"
-
-
-def gate_up_geglu(x: torch.Tensor, w_gu_interleaved: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``geglu(x @ w_gu^T)`` in one in-tree MFMA GEMM (gemm4 G4_GEGLU or ring RG_GEGLU) whose epilogue applies GeGLU to the fp32 accumulators
-    (rounded to bf16 first, so the result equals the unfused bf16 graph up to the GEMM's summation order);
-    ``w_gu_interleaved = w_gu[geglu_interleave_index(F)]``."""
-    M = x.numel() // x.shape[-1]
-    F = w_gu_interleaved.shape[0] // 2
-    if x.is_cuda:
-        out = _out(out, x.shape[:-1] + (F,), BF16, x.device)
-        c = _GD.choose(M, 2 * F, x.shape[-1], 3)
-        tb_gemm(x, w_gu_interleaved, out, None, None, 3, c if c != "blas" else _GD.fill_choice(M, 2 * F))
-        return out
-    inv = torch.argsort(geglu_interleave_index(F))
-    y = ref.geglu((x.reshape(M, -1).float() @ w_gu_interleaved[inv].float().T).to(BF16)).view(x.shape[:-1] + (F,))
-    if out is not None:
-        out.copy_(y)
-        return out
-    return y
 
 
 def lowrank_edit(h, apply, idx, cnt, E, Dm, bias=None, thr=None, pre_bias=None, alpha=1.0, w_next=None, eps=1e-6,

@@ -1,7 +1,9 @@
 """Per-shape GEMM selection between the in-tree MFMA kernels (four-wave, ring) and hipBLASLt.
 
-Every plain projection of the Gemma-2 forward (QKV, o, gate|up, down, lm_head / lens unembedding) goes
-through :func:`taboo_brittleness_amd.ops.linear`, which asks :func:`choose` for one of
+Every projection of the Gemma-2 forward (QKV, o, gate|up, down, lm_head / lens unembedding, the SAE encode, and their
+two-source LoRA forms) goes through ``taboo_brittleness_amd.ops.gemm``, which asks :func:`plan` for its launches: the
+table's choice (:func:`choose`), the per-epilogue rules (written down once, in :func:`plan`'s docstring) and the
+``"gs"`` row split.  Only :func:`parse_choice` reads choice strings.  Pure Python: no torch, no extension.  A choice is
 
 * ``"g256"`` / ``"g128"`` — ``csrc/gemm4.hip``'s four-wave kernel (128x128 wave tiles) with 256- or 128-row output
   tiles (the 128-row tile doubles the workgroup count for the N = 3584 projections at moderate M), bit-identical; ``"gs"`` — the four-wave kernel with its tile height(s) from a rounds model
@@ -34,7 +36,7 @@ import bisect
 import functools
 import json
 import os
-from typing import Dict, List, Optional, Tuple, Union
+from typing import Dict, List, NamedTuple, Optional, Tuple, Union
 
 REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 TABLE_DIR = os.path.join(REPO, "configs", "gemm_dispatch")
@@ -58,7 +60,6 @@ def mode() -> str:
 def load_table(path: Optional[str] = None, arch: str = "gemma2-9b") -> Optional[str]:
     """Load the measured dispatch table (``None``: ``TB_GEMM_TABLE`` or ``configs/gemm_dispatch/<arch>.json``)."""
     path = path or os.environ.get("TB_GEMM_TABLE") or os.path.join(TABLE_DIR, f"{arch}.json")
-    _state["loaded"] = True
     if not os.path.exists(path):
         _state["table"], _state["table_path"] = None, None
         return None
@@ -91,20 +92,11 @@ def choose(M: int, N: int, K: int, epi: int = 0) -> Choice:
         return "blas"
     if not _state["loaded"]:
         load_table()          # keyed by (N, K, epilogue): shapes of other models simply miss it
-    if m == "tb":
-        ent = _tb_entry(N, K, epi)
-        if ent is not None:
-            ms, cs = ent
-            return cs[min(bisect.bisect_left(ms, M), len(cs) - 1)]
-        return fill_choice(M, N)
-    tab = _state["table"]
-    if tab is not None:
-        ent = tab.get((N, K, epi))
-        if ent is not None:
-            ms, cs = ent
-            i = bisect.bisect_left(ms, M)
-            return cs[min(i, len(cs) - 1)]
-    return "blas"
+    ent = _tb_entry(N, K, epi) if m == "tb" else (_state["table"] or {}).get((N, K, epi))
+    if ent is not None:
+        ms, cs = ent
+        return cs[min(bisect.bisect_left(ms, M), len(cs) - 1)]
+    return fill_choice(M, N) if m == "tb" else "blas"
 
 
 @functools.lru_cache(maxsize=1024)
@@ -164,22 +156,111 @@ def split_rows(M: int, N: int) -> int:
     return min(cands, key=lambda m1: (cost(m1), -m1))
 
 
+class Parsed(NamedTuple):
+    """A choice, decoded: kind ``"g"`` / ``"k"`` (tile: tile rows), ``"r"`` (tile: ``(bm, bn, variant)``), ``"gs"``,
+    ``"blas"``."""
+    kind: str
+    tile: Union[None, int, Tuple[int, int, int]] = None
+
+
+class Launch(NamedTuple):
+    """One launch over rows ``[r0, r1)``: family ``"g4"`` / ``"splitk"`` (tile: tile rows), ``"ring"`` (tile:
+    ``(bm, bn, variant)``) or ``"blas"``."""
+    family: str
+    r0: int
+    r1: int
+    tile: Union[None, int, Tuple[int, int, int]] = None
+
+
+@functools.lru_cache(maxsize=512, typed=True)
+def parse_choice(c) -> Parsed:
+    """Every accepted spelling of a choice as one :class:`Parsed` value (the only place choice strings are read):
+    ``"g256"`` / ``"g128"``, ``"gs"``, ``"k64"`` / ``"k128"`` / ``"k256"``, ``"r<bm>x<bn>"`` (variant 0, 64 KB ring) /
+    ``"r<bm>x<bn>b"`` (1, 144 KB ring) / ``"r<bm>x<bn>c"`` (2, 144 KB ring of 4-8 K tiles per stage), ``"blas"``, a bare
+    table int ``256`` / ``128`` (= ``g<int>``); a :class:`Parsed` passes through."""
+    if isinstance(c, Parsed):
+        return c
+    if isinstance(c, int) and not isinstance(c, bool):
+        return Parsed("g", c)
+    if isinstance(c, str):
+        if c in ("gs", "blas"):
+            return Parsed(c)
+        head, body = c[:1], c[1:]
+        if head in ("g", "k") and body.isdigit():
+            return Parsed(head, int(body))
+        if head == "r":
+            var = {"b": 1, "c": 2}.get(body[-1:], 0)
+            bm, _, bn = (body[:-1] if var else body).partition("x")
+            if bm.isdigit() and bn.isdigit():
+                return Parsed("r", (int(bm), int(bn), var))
+    raise ValueError(f"unknown GEMM choice {c!r}")
+
+
 def is_invariant(choice: Choice) -> bool:
     """Whether a choice accumulates every output over K in the one order of the in-tree kernels (no split-K, no
     hipBLASLt): rows then get bit-identical results in any batch."""
-    return isinstance(choice, str) and choice[:1] in ("g", "r")   # incl. "gs"
+    return isinstance(choice, str) and parse_choice(choice).kind in ("g", "gs", "r")
 
 
 def ring_tile(choice: Choice) -> Optional[Tuple[int, int, int]]:
-    """``(bm, bn, variant)`` of a ring-GEMM choice ``"r<bm>x<bn>"`` (variant 0, 64 KB ring) / ``"r<bm>x<bn>b"``
-    (variant 1, 144 KB ring) / ``"r<bm>x<bn>c"`` (variant 2, 144 KB ring of 4-8 K tiles per stage, small tiles),
-    else None."""
-    if not (isinstance(choice, str) and choice[:1] == "r"):
-        return None
-    sfx = {"b": 1, "c": 2}.get(choice[-1], 0)
-    body, var = (choice[1:-1], sfx) if sfx else (choice[1:], 0)
-    bm, bn = body.split("x")
-    return int(bm), int(bn), var
+    """``(bm, bn, variant)`` of a ring-GEMM choice (see :func:`parse_choice`), else None."""
+    p = parse_choice(choice) if isinstance(choice, str) else None
+    return p.tile if p is not None and p.kind == "r" else None
+
+
+def resolve(M: int, N: int, K: int, epi: int = 0, two_source: bool = False, ring_ok=None) -> Parsed:
+    """The choice one GEMM runs, by the rules of :func:`plan`."""
+    if two_source:
+        c = choose(M, N, K, epi)
+        p = parse_choice(c) if isinstance(c, str) else None
+        if p is not None and p.kind == "r":
+            bm, bn, _ = p.tile
+            p = Parsed("r", (bm, bn, 1)) if ring_ok(epi if epi in (3, 4) else 0, bm, bn, 1) else None
+        return parse_choice(fill_choice(M, N)) if p is None or p.kind in ("blas", "k") else p
+    if epi in (4, 5) and not (has_entry(N, K, epi, M) or _state["mode"] == "tb"):
+        p = parse_choice(choose(M, N, K, 0))
+    else:
+        p = parse_choice(choose(M, N, K, epi))
+    if epi == 3 and p.kind == "blas":
+        return parse_choice(fill_choice(M, N))
+    if epi == 4 and p.kind == "r" and not ring_ok(4, *p.tile):
+        return Parsed("g", 128)
+    return p
+
+
+@functools.lru_cache(maxsize=4096)
+def _launches(p: Parsed, M: int, N: int) -> Tuple[Launch, ...]:
+    if p.kind == "gs":                # full rounds of 256-row tiles, the rest on 128-row tiles
+        M1 = split_rows(M, N)
+        return tuple(Launch("g4", r0, r1, rows) for r0, r1, rows in ((0, M1, 256), (M1, M, 128)) if r1 > r0)
+    return (Launch({"g": "g4", "k": "splitk", "r": "ring", "blas": "blas"}[p.kind], 0, M, p.tile),)
+
+
+def plan(M: int, N: int, K: int, epi: int = 0, two_source: bool = False, ring_ok=None,
+         choice: Optional[Choice] = None) -> Tuple[Launch, ...]:
+    """The launches of ``C[M, N] = A[M, K] @ W[N, K]^T`` under table key ``epi`` (0 plain, 3 gate|up + GeGLU,
+    4 QKV + RoPE, 5 o / down + residual norm), in order.  ``two_source``: A is ``[x | a2]`` (the LoRA-augmented
+    operand, ``K`` its whole width).  ``ring_ok(epi, bm, bn, variant)`` tells whether the ring GEMM is built with a
+    tile for this shape.  ``choice`` forces a choice in place of the rules (``ops.tb_gemm`` / ``ops.gemm_l2a``,
+    ``ops.linear``'s override).  The rules:
+
+    * epilogue 0 and 3: ``choose(M, N, K, epi)``.  For 3 that is also what ``ops.fused_geglu_wins`` tests
+      (``!= "blas"``); ``ops.gate_up_geglu``, once called, runs ``"blas"`` as ``fill_choice(M, N)``.
+    * epilogues 4 and 5: their own table entry where ``has_entry(N, K, epi, M)`` or the mode is ``tb``, else the
+      epilogue-0 entry.
+    * QKV (4), one source: a ring tile the kernel does not have (``ring_ok``) becomes the four-wave kernel with 128-row
+      tiles; ``"splitk"`` means fp32 partials summed by ``rope_qkv_cache_part``, ``"blas"`` the plain projection (its
+      own epilogue-0 dispatch) then ``rope_qkv_cache``.  For epilogue 5 ``"splitk"`` means partials summed by
+      ``add_rmsnorm2_part``.
+    * two sources: ``choose(M, N, K, epi)`` directly, without the epilogue-0 fallback; ``"blas"``, ``k*`` and bare-int
+      entries become ``fill_choice(M, N)`` (one K order, never hipBLASLt); a ring tile always takes variant 1 (the
+      only one built with two sources) and is checked with ``ring_ok`` -- epilogue 5 against ring epilogue 0 -- else
+      ``fill_choice(M, N)``.
+    * ``"gs"`` is two launches split at ``split_rows(M, N)``, empty row ranges dropped.
+    * a plain projection (0, 3, 5) with a ring choice does not ask ``ring_ok``: the binding checks the tile.
+    * ``ops.gemm_nt`` on four-wave-eligible shapes forces ``fill_choice(max(M, 4096), N)``."""
+    p = resolve(M, N, K, epi, two_source, ring_ok) if choice is None else parse_choice(choice)
+    return _launches(p, M, N)
 
 
 def describe() -> dict:

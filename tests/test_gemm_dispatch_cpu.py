@@ -81,3 +81,53 @@ def test_split_rows_rounds_model():
     assert GD.split_rows(2048, 3584) == 0       # 112 tiles: 224 of 128 rows still fit one round
     assert GD.split_rows(4096, 28672) == 4096   # 1792 tiles = 7 whole rounds
     assert GD.split_rows(4200, 8192) == 4096    # 32 x 17 = 544 tiles: 2 rounds + 32 128-row tiles
+
+
+def test_parse_choice_every_spelling():
+    P = GD.Parsed
+    for c, want in [("g256", P("g", 256)), ("g128", P("g", 128)), (256, P("g", 256)), (128, P("g", 128)),
+                    ("gs", P("gs")), ("blas", P("blas")), ("k64", P("k", 64)), ("k128", P("k", 128)),
+                    ("k256", P("k", 256)), ("r64x32", P("r", (64, 32, 0))), ("r128x64b", P("r", (128, 64, 1))),
+                    ("r16x16c", P("r", (16, 16, 2))), ("r64x112b", P("r", (64, 112, 1)))]:
+        assert GD.parse_choice(c) == want, c
+        assert GD.parse_choice(want) == want
+    for bad in ("", "x", "g", "gx", "r64", "r64x", "rx32b", "blass", None, 1.5, True):
+        try:
+            GD.parse_choice(bad)
+        except ValueError:
+            continue
+        raise AssertionError(f"{bad!r} parsed")
+
+
+def test_plan_rules(tmp_path):
+    """``plan`` on a small table: a two-source ring choice takes variant 1 (whatever the entry's) and is checked
+    against the ring epilogue, epilogue 5 falls back to the epilogue-0 entry (one source only), ``gs`` splits."""
+    p = tmp_path / "t.json"
+    json.dump({"shapes": {"3584,4096,0": [[64, "r32x32c"], [512, "k128"], [8192, "gs"]],
+                          "3584,4224,5": [[64, "r32x32c"]], "8192,3584,4": [[64, "r16x64"]]}}, open(p, "w"))
+    L, asked = GD.Launch, []
+
+    def ring_ok(epi, bm, bn, var, ok=True):
+        asked.append((epi, bm, bn, var))
+        return ok
+    old = GD.mode()
+    try:
+        GD.set_mode("auto")
+        GD.load_table(str(p))
+        assert GD.plan(64, 3584, 4224, 5, two_source=True, ring_ok=ring_ok) == (L("ring", 0, 64, (32, 32, 1)),)
+        assert asked == [(0, 32, 32, 1)]
+        no = lambda *a: ring_ok(*a, ok=False)                                                  # noqa: E731
+        assert GD.plan(64, 3584, 4224, 5, two_source=True, ring_ok=no) == (L("g4", 0, 64, 128),)
+        assert GD.plan(64, 3584, 4224, 0, two_source=True, ring_ok=ring_ok) == (L("g4", 0, 64, 128),)   # no entry: fill
+        assert GD.plan(64, 3584, 4096, 5) == (L("ring", 0, 64, (32, 32, 2)),)              # epilogue-0 entry, no ring_ok
+        assert GD.plan(300, 3584, 4096, 5) == (L("splitk", 0, 300, 128),)
+        assert GD.plan(6144, 3584, 4096, 0) == (L("g4", 0, 4608, 256), L("g4", 4608, 6144, 128))
+        assert GD.plan(2048, 3584, 4096, 0) == (L("g4", 0, 2048, 128),)                    # gs with an empty range
+        assert GD.plan(100, 3584, 14336, 0) == (L("blas", 0, 100, None),)
+        assert GD.plan(100, 28672, 3584, 3) == (L("g4", 0, 100, 128),)                     # gate_up_geglu: blas -> fill
+        assert GD.plan(64, 8192, 3584, 4, ring_ok=ring_ok) == (L("ring", 0, 64, (16, 64, 0)),)
+        assert GD.plan(64, 8192, 3584, 4, ring_ok=no) == (L("g4", 0, 64, 128),)
+        assert GD.plan(64, 8192, 3584, choice="r16x64b") == (L("ring", 0, 64, (16, 64, 1)),)
+    finally:
+        GD.set_mode(old)
+        GD._state["loaded"] = False

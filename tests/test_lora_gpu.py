@@ -109,19 +109,68 @@ def test_gemm_l2a_bitexact(gpu, epi):
         w = (torch.randn(N, k0 + 128, generator=g) * 0.02).to(BF).to(gpu)
         xc = torch.cat([x, a2], 1).contiguous()
         nout = N // 2 if epi == 3 else N
-        choices = ["g256", "g128", "gs"] + [("r", bm, bn) for bm, bn in ((16, 64), (64, 64), (128, 128), (64, 112))
+        choices = ["g256", "g128", "gs"] + [f"r{bm}x{bn}b" for bm, bn in ((16, 64), (64, 64), (128, 128), (64, 112))
                                               if _k_ring_ok(M, N, k0 + 128, epi, bm, bn)]
         for c in choices:
             got = torch.empty(M, nout, dtype=BF, device=gpu)
             ops.gemm_l2a(x, a2, w, got, epi, c)
             want = torch.empty(M, nout, dtype=BF, device=gpu)
-            ops.tb_gemm(xc, w, want, None, None, epi, c if isinstance(c, str) else f"r{c[1]}x{c[2]}b")
+            ops.tb_gemm(xc, w, want, None, None, epi, c)
             assert torch.equal(got, want), (M, N, k0, c)
     assert GD.ring_tile("r64x112b") == (64, 112, 1)
 
 
 def _k_ring_ok(M, N, K, epi, bm, bn):
     return ops._k().gemm_ring_ok(M, N, K, epi, bm, bn, 1)
+
+
+@pytest.mark.parametrize("epi", [0, 3, 4])
+def test_split_plan_bitexact(gpu, epi):
+    """The executor at the smallest shape where the ``gs`` plan has two non-empty launches (N = 8192, M = 2100: rows
+    [0, 2048) on 256-row tiles, the rest on 128-row tiles): with one A source and with two, the forced ``g256``,
+    ``gs`` and ring plans equal the ``g128`` one bit for bit (C, or q and the written K / V cache), and two sources
+    equal one source on the materialised concatenation.  epi 0 plain, 3 GeGLU (F = 4096), 4 QKV + RoPE (16 / 8
+    heads)."""
+    from taboo_brittleness_amd.runtime import gemm_dispatch as GD
+
+    M, N, k0, KP = 2100, 8192, 256, 128
+    Hq, Hkv, HD, S = 16, 8, 256, 8
+    assert GD.split_rows(M, N) == 2048 and len(GD.plan(M, N, k0, choice="gs")) == 2
+    g = torch.Generator().manual_seed(23 + epi)
+    x = torch.randn(M, k0, generator=g).to(BF).to(gpu)
+    a2 = (torch.randn(M, KP, generator=g) * 0.5).to(BF).to(gpu)
+    w = (torch.randn(N, k0 + KP, generator=g) * 0.05).to(BF).to(gpu)
+    pos = torch.randint(0, S, (M,), generator=g).int().to(gpu)
+    slot = torch.randperm(M, generator=g).int().to(gpu)            # one (slot, pos) per row: no write races
+    pos[1] = -1
+    cos_t, sin_t = (t.contiguous() for t in ref.rope_tables(HD, S, 10000.0, gpu))
+    cs = ops.rope_cs(cos_t, sin_t)
+
+    def run(xa, a2a, wa, c):
+        p = GD.plan(M, N, wa.shape[1], choice=c)
+        if epi != 4:
+            out = torch.empty(M, N // 2 if epi == 3 else N, dtype=BF, device=gpu)
+            ops.run_plan(p, xa, wa, out, epi, a2=a2a)
+            return (out,)
+        q = torch.zeros(M, Hq, HD, dtype=BF, device=gpu)
+        kc = torch.zeros(M, Hkv, S, HD, dtype=BF, device=gpu)
+        vc = torch.zeros_like(kc)
+        ops.run_plan(p, xa, wa, q, 4, a2=a2a, rope=(pos, slot, cs, kc, vc, Hq, Hkv))
+        return q, kc, vc
+
+    def ring(K):
+        tiles = [(bm, bn) for bm, bn in ops._k().gemm_ring_tiles(epi) if _k_ring_ok(M, N, K, epi, bm, bn)]
+        assert tiles, "no ring tile for this shape"
+        return "r%dx%db" % tiles[-1]
+
+    for xa, a2a, wa in ((x, None, w[:, :k0].contiguous()), (x, a2, w)):
+        want = run(xa, a2a, wa, "g128")
+        assert all(t.float().abs().sum() > 0 for t in want)
+        for c in ("g256", "gs", ring(wa.shape[1])):
+            for a, b in zip(run(xa, a2a, wa, c), want):
+                assert torch.equal(a, b), (epi, a2a is not None, c)
+    for a, b in zip(run(torch.cat([x, a2], 1).contiguous(), None, w, "g128"), want):
+        assert torch.equal(a, b), epi
 
 
 def test_qkv_rope_l2a_bitexact(gpu, tb_gemm):

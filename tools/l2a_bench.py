@@ -1,6 +1,6 @@
 """Two-source (LoRA K-augmented) GEMMs vs the single-source GEMM of the materialised concatenation, same kernel
-choice (ops._l2a_choice), Gemma-2-9B projection shapes + KP = 128: GPU time per call from a hipGraph of 10 calls,
-median of 5 replays, outputs compared bit for bit.  The ratio is the price of reading [x | T] from two sources."""
+choice (runtime.gemm_dispatch.resolve, two sources), Gemma-2-9B projection shapes + KP = 128: GPU time per call from a
+hipGraph of 10 calls, median of 5 replays, outputs compared bit for bit.  The ratio is the price of reading [x | T] from two sources."""
 import json
 import sys
 
@@ -8,6 +8,7 @@ import torch
 
 sys.path.insert(0, ".")
 from taboo_brittleness_amd import ops  # noqa: E402
+from taboo_brittleness_amd.runtime import gemm_dispatch as GD  # noqa: E402
 
 BF = torch.bfloat16
 SHAPES = {"gu": (28672, 3584, 3), "o": (3584, 4096, 0), "down": (3584, 14336, 0)}   # name -> (N, K0, epi)
@@ -40,15 +41,15 @@ def main():
             x = torch.randn(M, K0, device=dev).to(BF)
             t = (torch.randn(M, KP, device=dev) * 0.5).to(BF)
             xc = torch.cat([x, t], 1).contiguous()
-            c = ops._l2a_choice(M, N, K0 + KP, epi)
+            K = K0 + KP
+            c = GD.resolve(M, N, K, epi, True, lambda e, bm, bn, v: ops._k().gemm_ring_ok(M, N, K, e, bm, bn, v))
             nout = N // 2 if epi == 3 else N
             o1 = torch.empty(M, nout, dtype=BF, device=dev)
             o2 = torch.empty(M, nout, dtype=BF, device=dev)
-            cs = c if isinstance(c, str) else f"r{c[1]}x{c[2]}b"
             t1 = timed(lambda: ops.gemm_l2a(x, t, w, o1, epi, c))
-            t2 = timed(lambda: ops.tb_gemm(xc, w, o2, None, None, epi, cs))
+            t2 = timed(lambda: ops.tb_gemm(xc, w, o2, None, None, epi, c))
             assert torch.equal(o1, o2), (name, M, c)
-            print(json.dumps({"proj": name, "M": M, "choice": cs, "l2a_us": round(t1, 2), "single_us": round(t2, 2),
+            print(json.dumps({"proj": name, "M": M, "choice": list(c), "l2a_us": round(t1, 2), "single_us": round(t2, 2),
                               "ratio": round(t1 / t2, 4)}), flush=True)
 
 

@@ -132,19 +132,9 @@ def main():
                         var[rname(bm, bn, rv)] = (lambda bm_, bn_, rv_: lambda: k.gemm_ring_qkv_rope(
                             A, nxt(), pos, slot, cs, q, kc, vc, Hq, Hkv, bm_, bn_, rv_))(bm, bn, rv)
                     for ch in others:
-                        if ch == "gs":
-                            M1 = GD.split_rows(M, N)
-
-                            def rope_split(M1=M1):
-                                w_ = nxt()
-                                for r0, r1, tr in ((0, M1, 256), (M1, M, 128)):
-                                    if r1 > r0:
-                                        k.gemm4_qkv_rope(A[r0:r1], w_, pos[r0:r1], slot[r0:r1], cs, q[r0:r1],
-                                                         kc, vc, Hq, Hkv, tr)
-                            var[ch] = rope_split
-                        elif ch.startswith("g"):
-                            var[ch] = (lambda r_: lambda: k.gemm4_qkv_rope(A, nxt(), pos, slot, cs, q, kc, vc,
-                                                                           Hq, Hkv, r_))(int(ch[1:]))
+                        if ch.startswith("g"):        # "g256" / "g128" / "gs": the executor with a forced choice
+                            var[ch] = (lambda p_: lambda: ops.run_plan(
+                                p_, A, nxt(), q, 4, rope=(pos, slot, cs, kc, vc, Hq, Hkv)))(GD.plan(M, N, K, choice=ch))
                     var["blas"] = lambda: (torch.matmul(A, nxt().t(), out=C),
                                            ops.rope_qkv_cache(C, pos, slot, cos_t, sin_t, kc, vc, Hq, Hkv, HD, q_out=q))
                 else:
