@@ -1,5 +1,6 @@
 """``python -m taboo_brittleness_amd.cli.run_sweep [cfg] [--methods sae|proj|all]`` — targeted-vs-random
-SAE-latent ablation and low-rank projection sweeps (EP:112-152).  Multi-GPU:
+SAE-latent ablation and low-rank projection sweeps (EP:112-152); ``--methods sae_noise|proj_noise|all_noise`` add the
+norm-matched controls, ``--methods sae_swap|proj_swap|swap`` the interchange (donor-swap) methods.  Multi-GPU:
 ``python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m taboo_brittleness_amd.cli.run_sweep cfg``."""
 import os
 
@@ -13,6 +14,10 @@ METHOD_SETS = {"sae": ("sae_targeted", "sae_random"), "proj": ("proj_targeted", 
 METHOD_SETS.update({"sae_noise": METHOD_SETS["sae"] + ("sae_noise",),
                     "proj_noise": METHOD_SETS["proj"] + ("proj_noise",),
                     "all_noise": METHOD_SETS["all"] + ("sae_noise", "proj_noise")})
+# each set plus its interchange (donor-swap) methods (pipelines/sweep_types.py SWAP_METHODS; intervention.swap_donor)
+METHOD_SETS.update({"sae_swap": METHOD_SETS["sae"] + ("sae_swap", "sae_swap_random"),
+                    "proj_swap": METHOD_SETS["proj"] + ("proj_swap", "proj_swap_random"),
+                    "swap": METHOD_SETS["all"] + ("sae_swap", "sae_swap_random", "proj_swap", "proj_swap_random")})
 
 
 def main(argv=None):

@@ -142,6 +142,10 @@ class InterventionCfg:
     # draws per budget / rank of the norm-matched controls sae_noise / proj_noise (opt-in methods,
     # pipelines/sweep_types.py)
     noise_trials: int = 5
+    # donor of the interchange methods sae_swap* / proj_swap* (opt-in, pipelines/sweep_types.py): "next_word" (the next
+    # word's pair with the same prompt: does the edit carry *which* secret it is?) or "next_prompt" (the same word's
+    # next prompt, the specificity control: the same secret from another context should stay readable)
+    swap_donor: str = "next_word"
     score_over: str = "prompt"          # "prompt" (per prompt) or "word" (average over prompts)
     # how the targeted latents are ranked: "corr" (EP:118-124: spike-mean activation x positive correlation with the
     # secret probability), or by what ablating the latent alone does at the spikes: "effect_lens" (the exact drop of

@@ -100,6 +100,14 @@ void tb_lowrank_edit(uint16_t* h, uint16_t* x_next, const uint8_t* apply, const 
                      int mmax, const void* E, const void* Dm, int table_f32, const float* bias, const float* thr,
                      const float* pre_bias, float alpha, const uint16_t* w_next, float eps, int M, int D,
                      float* coef_out, hipStream_t st, const float* val = nullptr);
+// interchange_edit (the same kernel family): c_j = fl32(alpha a_j(h)) - fl32(alpha a_j(donor[src[row]])), donor
+// [n_donor, D] bf16, src [M] int32 (outside [0, n_donor): row untouched); coef_out / dcoef_out (optional) = a_j(h) /
+// a_j(donor row)
+void tb_interchange_edit(uint16_t* h, uint16_t* x_next, const uint8_t* apply, const int32_t* idx, const int32_t* cnt,
+                         int mmax, const void* E, const void* Dm, int table_f32, const float* bias, const float* thr,
+                         const float* pre_bias, float alpha, const uint16_t* w_next, float eps, int M, int D,
+                         float* coef_out, const uint16_t* donor, const int32_t* src, int n_donor, float* dcoef_out,
+                         hipStream_t st);
 // matched_noise.hip: the norm-matched control of lowrank_edit (val null) / latent_affine_edit: the rows they would
 // edit move by n = |sum_j c_j Dm[idx_j]|_2 along z / |z|_2, z_d = rb_gauss(seeds[row], pos[row], d); rows they leave
 // alone stay bit-identical.  norm_out [M] (optional) = n, 0 on the untouched rows.

@@ -699,15 +699,21 @@ struct NoiseArgs {
   c10::optional<torch::Tensor> norm_out;
 };
 
+// What interchange_edit takes on top of lowrank_edit
+struct SwapArgs {
+  torch::Tensor donor, src;
+  c10::optional<torch::Tensor> dcoef_out;
+};
+
 // lowrank_edit and, with val [M, mmax] fp32, latent_affine_edit (one kernel family, csrc/sae.hip); with noise, the
-// norm-matched control of either (csrc/matched_noise.hip)
+// norm-matched control of either (csrc/matched_noise.hip); with swap, interchange_edit (the same family)
 static void lowrank_edit_impl(torch::Tensor h, c10::optional<torch::Tensor> x_next, torch::Tensor apply,
                               torch::Tensor idx, torch::Tensor cnt, torch::Tensor E, torch::Tensor Dm,
                               c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> thr,
                               c10::optional<torch::Tensor> pre_bias, double alpha,
                               c10::optional<torch::Tensor> w_next, double eps,
                               c10::optional<torch::Tensor> coef_out, const torch::Tensor* val,
-                              const NoiseArgs* noise = nullptr) {
+                              const NoiseArgs* noise = nullptr, const SwapArgs* swap = nullptr) {
   IN_BF16(h); IN_U8(apply); IN_I32(idx); IN_I32(cnt); CHECK_DEV(E); CHECK_CONTIG(E); CHECK_DEV(Dm);
   CHECK_CONTIG(Dm);
   TORCH_CHECK(E.scalar_type() == Dm.scalar_type(), "E/D dtype mismatch");
@@ -769,6 +775,26 @@ static void lowrank_edit_impl(torch::Tensor h, c10::optional<torch::Tensor> x_ne
                           noise->pos.data_ptr<int32_t>(), no, cur_stream());
     return;
   }
+  if (swap != nullptr) {
+    IN_BF16(swap->donor); IN_I32(swap->src);
+    TORCH_CHECK(swap->donor.dim() == 2 && swap->donor.size(1) == D,
+                "interchange_edit: donor must be [R, D] bf16 with h's width");
+    TORCH_CHECK(swap->donor.size(0) < (int64_t)1 << 31, "interchange_edit: donor rows");
+    TORCH_CHECK(swap->src.numel() == M, "interchange_edit: src must be [rows] int32");
+    float* dc = nullptr;
+    if (swap->dcoef_out.has_value() && swap->dcoef_out->defined()) {
+      IN_F32((*swap->dcoef_out));
+      TORCH_CHECK(swap->dcoef_out->numel() >= (int64_t)M * mmax,
+                  "interchange_edit: dcoef_out smaller than [rows, mmax]");
+      dc = swap->dcoef_out->data_ptr<float>();
+    }
+    c10::DeviceGuard g(h.device());
+    tb_interchange_edit(bf(h), xn, reinterpret_cast<const uint8_t*>(apply.data_ptr()), idx.data_ptr<int32_t>(),
+                        cnt.data_ptr<int32_t>(), mmax, E.data_ptr(), Dm.data_ptr(), f32 ? 1 : 0, optf(bias),
+                        optf(thr), optf(pre_bias), (float)alpha, wn, (float)eps, M, D, co, cbf(swap->donor),
+                        swap->src.data_ptr<int32_t>(), (int)swap->donor.size(0), dc, cur_stream());
+    return;
+  }
   c10::DeviceGuard g(h.device());
   tb_lowrank_edit(bf(h), xn, reinterpret_cast<const uint8_t*>(apply.data_ptr()), idx.data_ptr<int32_t>(),
                   cnt.data_ptr<int32_t>(), mmax, E.data_ptr(), Dm.data_ptr(), f32 ? 1 : 0, optf(bias), optf(thr),
@@ -803,6 +829,18 @@ void matched_noise_edit(torch::Tensor h, c10::optional<torch::Tensor> x_next, to
   const bool aff = val.has_value() && val->defined();
   lowrank_edit_impl(h, x_next, apply, idx, cnt, E, Dm, bias, thr, pre_bias, alpha, w_next, eps, coef_out,
                     aff ? &*val : nullptr, &noise);
+}
+
+// Interchange (donor-swap) edit: h -= sum_j (fl32(alpha a_j(h)) - fl32(alpha a_j(donor[src[row]]))) Dm[idx_j] on the
+// flagged rows whose src lies in [0, R); coef_out / dcoef_out [rows, mmax] fp32 receive a_j(h) / a_j(donor row)
+void interchange_edit(torch::Tensor h, c10::optional<torch::Tensor> x_next, torch::Tensor apply, torch::Tensor idx,
+                      torch::Tensor cnt, torch::Tensor E, torch::Tensor Dm, torch::Tensor donor, torch::Tensor src,
+                      c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> thr,
+                      c10::optional<torch::Tensor> pre_bias, double alpha, c10::optional<torch::Tensor> w_next,
+                      double eps, c10::optional<torch::Tensor> coef_out, c10::optional<torch::Tensor> dcoef_out) {
+  const SwapArgs swap{donor, src, dcoef_out};
+  lowrank_edit_impl(h, x_next, apply, idx, cnt, E, Dm, bias, thr, pre_bias, alpha, w_next, eps, coef_out, nullptr,
+                    nullptr, &swap);
 }
 
 // Reconstruct-mode splice (csrc/sae.hip): acts [R, L] fp32 activation rows, src_row [M] int32 (optional) the
@@ -1205,6 +1243,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lowrank_edit", &lowrank_edit);
   m.def("latent_affine_edit", &latent_affine_edit);
   m.def("matched_noise_edit", &matched_noise_edit);
+  m.def("interchange_edit", &interchange_edit);
   m.def("sae_decode_sparse", &sae_decode_sparse);
   m.def("sae_splice_edit", &sae_splice_edit);
   m.def("flag_compact", &flag_compact);

@@ -16,6 +16,8 @@
 //                   f = id it is the projection-out x - U U^T x (EP:148).
 //  latent_affine_edit  lowrank_edit with a per-row target: h += sum_j (val_j - alpha a_j) D_j, so a latent is
 //                   clamped (alpha = 1: held at val_j whether or not it fires) or steered (alpha = 0: val_j added).
+//  interchange_edit  lowrank_edit against a donor row: h -= sum_j alpha (a_j(h) - a_j(donor[src[row]])) D_j, so the
+//                   selected latents (or subspace coordinates) take the values they have in the donor run.
 //  sae_decode_sparse  x_hat = sum_{a_j != 0} a_j W_dec[j] + b_dec (L0 ~ 76 of 16k)
 //  sae_splice_edit  reconstruct-mode ablation (EP:126 literal): per flagged row h <- bf16(b_dec + sum over the
 //                   active latents, ascending, of s_j a_j W_dec[j]), s_j = 1 - alpha on the ablated ones, then
@@ -140,18 +142,28 @@ __global__ void __launch_bounds__(256) gemm_nt_kernel(const uint16_t* __restrict
 // (load8 and the coefficient stage live in lowrank_coef.h, shared with matched_noise.hip)
 // One workgroup (256 threads) per row; D <= 256*8*VPT.  AFF (latent_affine_edit): the row's coefficient becomes
 // alpha * a_j - val[row, j] = -delta_j, so h += sum_j delta_j D_j moves latent j from alpha * a_j to val_j.  The two
-// entry points share every other line, so val == 0 gives lowrank_edit's bits.
-template <typename TT, int VPT, bool AFF>
+// entry points share every other line, so val == 0 gives lowrank_edit's bits.  LR_SWAP (interchange_edit): the
+// coefficient is fl32(alpha * a_j(h)) - fl32(alpha * a_j(donor[src[row]])), so the selected coordinates move from the
+// row's own values to the donor's; a row whose src is outside the donor table is left alone.  Both products pass
+// through LDS before the subtraction, so a row that is its own donor is an exact no-op and the result is
+// latent_affine_edit's with val = alpha * a(donor), bit for bit.
+constexpr int LR_PLAIN = 0, LR_AFF = 1, LR_SWAP = 2;
+
+template <typename TT, int VPT, int VAR>
 __global__ void __launch_bounds__(256) lowrank_edit_kernel(
     uint16_t* __restrict__ h, uint16_t* __restrict__ x_next, const uint8_t* __restrict__ apply,
     const int32_t* __restrict__ idx, const int32_t* __restrict__ cnt, int mmax, const TT* __restrict__ E,
     const TT* __restrict__ Dm, const float* __restrict__ bias, const float* __restrict__ thr,
     const float* __restrict__ pre_bias, float alpha, const uint16_t* __restrict__ w_next, float eps, int D,
-    float* __restrict__ coef_out, const float* __restrict__ val) {
+    float* __restrict__ coef_out, const float* __restrict__ val, const uint16_t* __restrict__ donor,
+    const int32_t* __restrict__ src, int n_donor, float* __restrict__ dcoef_out) {
   const int row = blockIdx.x;
   if (!apply[row]) return;
+  const int sr = VAR == LR_SWAP ? src[row] : 0;
+  if (VAR == LR_SWAP && (sr < 0 || sr >= n_donor)) return;   // no donor row for this flag: leave the row alone
   __shared__ float red[16];
   __shared__ float coef[256];
+  __shared__ float dcoef[VAR == LR_SWAP ? 256 : 1];
   const int nvec = D >> 3;
   const int tid = threadIdx.x;
   uint16_t* hr = h + (size_t)row * D;
@@ -166,9 +178,17 @@ __global__ void __launch_bounds__(256) lowrank_edit_kernel(
   }
   const int m = min(cnt[row], min(mmax, 256));
   const int32_t* ir = idx + (size_t)row * mmax;
-  lowrank_coefs<TT, AFF>(hr, ir, m, nvec, E, D, bias, thr, pre_bias, alpha,
-                         coef_out ? coef_out + (size_t)row * mmax : nullptr,
-                         AFF ? val + (size_t)row * mmax : nullptr, coef);
+  if (VAR == LR_SWAP)
+    lowrank_coefs<TT, false>(donor + (size_t)sr * D, ir, m, nvec, E, D, bias, thr, pre_bias, alpha,
+                             dcoef_out ? dcoef_out + (size_t)row * mmax : nullptr, nullptr, dcoef);
+  lowrank_coefs<TT, VAR == LR_AFF>(hr, ir, m, nvec, E, D, bias, thr, pre_bias, alpha,
+                                   coef_out ? coef_out + (size_t)row * mmax : nullptr,
+                                   VAR == LR_AFF ? val + (size_t)row * mmax : nullptr, coef);
+  if (VAR == LR_SWAP) {
+    // both products are fp32 values in LDS here, so the subtraction cannot contract with either of them
+    if (tid < m) coef[tid] -= dcoef[tid];
+    __syncthreads();
+  }
   // an all-zero edit (every ablated latent below its threshold here, or alpha = 0) is an exact no-op: h and
   // x_next stay bit-identical to the unedited forward (no re-rounded h, no re-normalised x)
   bool any = false;
@@ -512,26 +532,50 @@ void tb_gemm_nt(const uint16_t* A, const uint16_t* W, void* C, const float* bias
   else hipLaunchKernelGGL(gemm_nt_kernel<2>, dim3(nwg), dim3(256), 0, st, A, W, C, bias, thr, M, N, K, ldc);
 }
 
+// the lowrank_edit_kernel family: val -> LR_AFF, donor -> LR_SWAP, neither -> LR_PLAIN
+static void launch_lowrank(uint16_t* h, uint16_t* x_next, const uint8_t* apply, const int32_t* idx,
+                           const int32_t* cnt, int mmax, const void* E, const void* Dm, int table_f32,
+                           const float* bias, const float* thr, const float* pre_bias, float alpha,
+                           const uint16_t* w_next, float eps, int M, int D, float* coef_out, hipStream_t st,
+                           const float* val, const uint16_t* donor, const int32_t* src, int n_donor,
+                           float* dcoef_out) {
+  if (M <= 0) return;
+  const int nvec = D >> 3;
+#define TB_LR(TT, VPT, VAR)                                                                                      \
+  hipLaunchKernelGGL((lowrank_edit_kernel<TT, VPT, VAR>), dim3(M), dim3(256), 0, st, h, x_next, apply, idx, cnt, \
+                     mmax, (const TT*)E, (const TT*)Dm, bias, thr, pre_bias, alpha, w_next, eps, D, coef_out, val, \
+                     donor, src, n_donor, dcoef_out)
+#define TB_LRV(TT, VAR)                                                                                  \
+  do {                                                                                                   \
+    if (nvec <= 256) TB_LR(TT, 1, VAR); else if (nvec <= 512) TB_LR(TT, 2, VAR); else TB_LR(TT, 4, VAR); \
+  } while (0)
+  if (donor != nullptr) {
+    if (table_f32) TB_LRV(float, LR_SWAP); else TB_LRV(uint16_t, LR_SWAP);
+  } else if (val != nullptr) {
+    if (table_f32) TB_LRV(float, LR_AFF); else TB_LRV(uint16_t, LR_AFF);
+  } else {
+    if (table_f32) TB_LRV(float, LR_PLAIN); else TB_LRV(uint16_t, LR_PLAIN);
+  }
+#undef TB_LRV
+#undef TB_LR
+}
+
 void tb_lowrank_edit(uint16_t* h, uint16_t* x_next, const uint8_t* apply, const int32_t* idx, const int32_t* cnt,
                      int mmax, const void* E, const void* Dm, int table_f32, const float* bias, const float* thr,
                      const float* pre_bias, float alpha, const uint16_t* w_next, float eps, int M, int D,
                      float* coef_out, hipStream_t st, const float* val) {
-  if (M <= 0) return;
-  const int nvec = D >> 3;
-#define TB_LR(TT, VPT, AFF)                                                                                      \
-  hipLaunchKernelGGL((lowrank_edit_kernel<TT, VPT, AFF>), dim3(M), dim3(256), 0, st, h, x_next, apply, idx, cnt, \
-                     mmax, (const TT*)E, (const TT*)Dm, bias, thr, pre_bias, alpha, w_next, eps, D, coef_out, val)
-#define TB_LRV(TT, AFF)                                                                                  \
-  do {                                                                                                   \
-    if (nvec <= 256) TB_LR(TT, 1, AFF); else if (nvec <= 512) TB_LR(TT, 2, AFF); else TB_LR(TT, 4, AFF); \
-  } while (0)
-  if (val != nullptr) {
-    if (table_f32) TB_LRV(float, true); else TB_LRV(uint16_t, true);
-  } else {
-    if (table_f32) TB_LRV(float, false); else TB_LRV(uint16_t, false);
-  }
-#undef TB_LRV
-#undef TB_LR
+  launch_lowrank(h, x_next, apply, idx, cnt, mmax, E, Dm, table_f32, bias, thr, pre_bias, alpha, w_next, eps, M, D,
+                 coef_out, st, val, nullptr, nullptr, 0, nullptr);
+}
+
+void tb_interchange_edit(uint16_t* h, uint16_t* x_next, const uint8_t* apply, const int32_t* idx, const int32_t* cnt,
+                         int mmax, const void* E, const void* Dm, int table_f32, const float* bias, const float* thr,
+                         const float* pre_bias, float alpha, const uint16_t* w_next, float eps, int M, int D,
+                         float* coef_out, const uint16_t* donor, const int32_t* src, int n_donor, float* dcoef_out,
+                         hipStream_t st) {
+  if (donor == nullptr || src == nullptr || n_donor <= 0) return;   // no donor table: every row is left alone
+  launch_lowrank(h, x_next, apply, idx, cnt, mmax, E, Dm, table_f32, bias, thr, pre_bias, alpha, w_next, eps, M, D,
+                 coef_out, st, nullptr, donor, src, n_donor, dcoef_out);
 }
 
 void tb_sae_decode_sparse(const float* acts, const void* Wdec, int table_f32, const float* b_dec, uint16_t* out_bf16,

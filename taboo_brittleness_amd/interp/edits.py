@@ -46,6 +46,19 @@ would move it (``|sum_j c_j D_j|_2``, the coefficients computed by the same devi
 direction drawn from ``(EditPlan.seeds[row], absolute position)``.  A position therefore gets the same edit in a
 prefill, a teacher-forced tail and a decode step, and a row where the targeted edit is an exact no-op is one for
 the control too.  ``reconstruct`` replaces the residual instead of adding a delta to it, so it has no such control.
+
+``sae_swap`` (kind 5) and ``proj_swap`` (kind 6) rows are *interchange interventions* (``ops.interchange_edit``): at
+the row's spike positions the selected latents (kind 5) or the coordinates in the span of the row's basis rows
+(kind 6) are set to the values they have in a *donor* residual, and everything else -- the SAE error, every other
+latent, the orthogonal complement -- stays.  Where the other kinds test necessity (does the readout drop when these
+coordinates go?), these test sufficiency and specificity (do they carry *which* secret it is?).  The donor rows
+live in ``EditPlan.donor [R, D]``; the donor of plan row ``b`` at its ``k``-th spike is ``donor[donor_base[b] + k]``
+(``donor_base < 0``: that row is left alone), which the hook resolves on the device as it does the activation table
+of the reconstruct mode, so the path stays static-shape and free of host syncs.  For ``sae_swap`` rows ``alpha``
+interpolates between the row's own activations (0) and the donor's (1); ``proj_swap`` rows take the donor's
+coordinates outright, as ``proj`` rows are projected out outright.  A row that equals its donor row is an exact
+no-op.  A swap row needs a donor per spike, so it cannot edit at ``ALL_POSITIONS``, and ``sae_swap`` is defined for
+the error-preserving mode only.  A plan without swap rows runs exactly the calls it ran before these kinds existed.
 """
 from __future__ import annotations
 
@@ -63,7 +76,8 @@ class EditPlan:
     """Device tensors, one row per sequence in the batch."""
 
     spikes: torch.Tensor                 # [B, K] int32 absolute positions, -1 = unused
-    kind: torch.Tensor                   # [B] int8: 0 none, 1 sae, 2 proj, 3 sae_noise, 4 proj_noise
+    kind: torch.Tensor                   # [B] int8: 0 none, 1 sae, 2 proj, 3 sae_noise, 4 proj_noise, 5 sae_swap,
+                                         # 6 proj_swap
     idx: torch.Tensor                    # [B, mmax] int32 (latent ids, or rows of the basis table)
     cnt: torch.Tensor                    # [B] int32
     alpha: float = 1.0
@@ -73,9 +87,27 @@ class EditPlan:
     values: Optional[torch.Tensor] = None  # [B, mmax] fp32 targets c of the selected latents (clamp / steer modes)
     seeds: Optional[torch.Tensor] = None   # [B] int64 noise streams of the sae_noise / proj_noise rows
     has_noise: tuple = (False, False)      # host-known: some row has kind 3 / kind 4 (set by build)
+    donor: Optional[torch.Tensor] = None   # [R, D] donor residuals of the sae_swap / proj_swap rows (model dtype)
+    # [B] int32: row b's k-th spike reads donor[donor_base[b] + k]; < 0: no donor
+    donor_base: Optional[torch.Tensor] = None
+    has_swap: tuple = (False, False)       # host-known: some row has kind 5 / kind 6 (set by build)
 
     def __post_init__(self):
         check_mode(self.mode)
+        if any(self.has_swap):
+            if self.donor is None or self.donor_base is None:
+                raise ValueError("EditPlan: sae_swap / proj_swap rows need donor ([R, D]) and donor_base ([B] int32)")
+            if self.any_position and bool(((self.kind >= 5).view(-1, 1) & (self.spikes == ALL_POSITIONS)).any()):
+                raise ValueError("EditPlan: sae_swap / proj_swap rows cannot be combined with ALL_POSITIONS spikes "
+                                 "(a donor row exists per spike only)")
+            if self.has_swap[0] and self.mode != "error_preserving":
+                raise ValueError(f"EditPlan: sae_swap is defined for ablation_mode = error_preserving only, not "
+                                 f"{self.mode!r}")
+        if self.donor is not None and self.donor.dim() != 2:
+            raise ValueError("EditPlan.donor must be [R, D]")
+        if self.donor_base is not None and (self.donor_base.dtype != torch.int32
+                                            or self.donor_base.numel() != self.kind.numel()):
+            raise ValueError("EditPlan.donor_base must be [B] int32")
         if any(self.has_noise):
             if self.seeds is None:
                 raise ValueError("EditPlan: sae_noise / proj_noise rows need seeds ([B] int64)")
@@ -98,11 +130,14 @@ class EditPlan:
     def build(device, spikes: Sequence[Sequence[int]], kinds: Sequence[str], sel: Sequence[Sequence[int]],
               alpha: float = 1.0, basis: Optional[torch.Tensor] = None, kmax: Optional[int] = None,
               mmax: Optional[int] = None, mode: str = "error_preserving", values=None, seeds=None,
-              noise: Optional[tuple] = None) -> "EditPlan":
+              noise: Optional[tuple] = None, donor: Optional[torch.Tensor] = None, donor_base=None,
+              swap: Optional[tuple] = None) -> "EditPlan":
         """``values`` (clamp / steer modes): the targets of the selected latents, one scalar for all of them or a
         per-row list of lists aligned with ``sel``.  ``seeds``: one int per row, required with ``sae_noise`` /
         ``proj_noise`` rows (taken mod 2^64).  ``noise``: which noise paths (``sae_noise``, ``proj_noise``) the hook
-        keeps, for a plan that is refilled in place; default: those of ``kinds``."""
+        keeps, for a plan that is refilled in place; default: those of ``kinds``.  ``donor [R, D]`` / ``donor_base``
+        (one int per row, < 0: no donor): the donor residuals of the ``sae_swap`` / ``proj_swap`` rows; ``swap``: which
+        swap paths the hook keeps, as ``noise``."""
         B = len(spikes)
         kmax = kmax or max(1, max((len(s) for s in spikes), default=1))
         mmax = mmax or max(1, max((len(s) for s in sel), default=1))
@@ -141,12 +176,19 @@ class EditPlan:
             if len(seeds) != B:
                 raise ValueError(f"EditPlan.build: seeds has {len(seeds)} rows, sel has {B}")
             sd = t(seeds_to_int64(seeds))
+        db = None
+        if donor_base is not None:
+            if len(donor_base) != B:
+                raise ValueError(f"EditPlan.build: donor_base has {len(donor_base)} rows, sel has {B}")
+            db = t(np.asarray([int(v) for v in donor_base], dtype=np.int32))
         return EditPlan(t(sp), t(kd), t(ix), t(cn), alpha, basis.to(device) if basis is not None else None, mode,
                         bool((sp == ALL_POSITIONS).any()), vals, sd,
-                        tuple(noise) if noise is not None else (bool((kd == 3).any()), bool((kd == 4).any())))
+                        tuple(noise) if noise is not None else (bool((kd == 3).any()), bool((kd == 4).any())),
+                        donor.to(device) if donor is not None else None, db,
+                        tuple(swap) if swap is not None else (bool((kd == 5).any()), bool((kd == 6).any())))
 
 
-KIND_CODES = {"none": 0, "sae": 1, "proj": 2, "sae_noise": 3, "proj_noise": 4}
+KIND_CODES = {"none": 0, "sae": 1, "proj": 2, "sae_noise": 3, "proj_noise": 4, "sae_swap": 5, "proj_swap": 6}
 
 
 def seeds_to_int64(seeds) -> np.ndarray:
@@ -215,6 +257,9 @@ class EditHook:
             if any(self.plan.has_noise):
                 b["apply_noise"] = torch.empty(B * T, dtype=torch.uint8, device=device)
                 b["seeds"] = torch.empty(B * T, dtype=torch.int64, device=device)
+            if any(self.plan.has_swap):
+                b["apply_swap"] = torch.empty(B * T, dtype=torch.uint8, device=device)
+                b["donor_src"] = torch.empty(B * T, dtype=torch.int32, device=device)
             if self.plan.mode == "reconstruct" and self.sae is not None:
                 b["src"] = torch.empty(B * T, dtype=torch.int32, device=device)
                 cap = self._capacity(B, T)
@@ -258,6 +303,33 @@ class EditHook:
                              ctx.w_next, ctx.eps, x, None)
         if any(pl.has_noise):
             self._noise(h, x, ctx, r, hit, kind, sl)
+        if any(pl.has_swap):
+            self._swap(h, x, ctx, r, hit, kind, sl, spikes)
+
+    def _swap(self, h, x, ctx, r, hit, kind, sl, spikes) -> None:
+        """The interchange rows: kind 5 with the SAE tables, kind 6 with the plan's basis.  ``src`` is the donor row
+        of the first matching spike (as :meth:`_splice` reads its table), -1 where the row is no flagged swap row."""
+        B, T = ctx.B, ctx.T
+        pl = self.plan
+        swap = hit & (kind >= 5)
+        k = (ctx.pos.view(B, T, 1) == spikes.view(B, 1, -1)).to(torch.int32).argmax(-1)          # first matching spike
+        b0 = pl.donor_base.index_select(0, sl).view(B, 1)
+        src = torch.where(b0 >= 0, b0 + k, torch.full_like(k, -1)).view(B * T)
+        r["donor_src"].copy_(torch.where(swap, src, torch.full_like(src, -1)))
+        if pl.has_swap[0]:
+            if self.sae is None:
+                raise ValueError("EditPlan has sae_swap rows but the hook has no SAE")
+            s = self.sae
+            r["apply_swap"].copy_(hit & (kind == 5))
+            ops.interchange_edit(h, r["apply_swap"], r["idx"], r["cnt"], s.W_encT, s.W_dec, pl.donor, r["donor_src"],
+                                 s.b_enc, s.threshold, s.b_dec if s.apply_b_dec_to_input else None, pl.alpha,
+                                 ctx.w_next, ctx.eps, x, r["coef"])
+        if pl.has_swap[1]:
+            if pl.basis is None:
+                raise ValueError("EditPlan has proj_swap rows but no basis")
+            r["apply_swap"].copy_(hit & (kind == 6))
+            ops.interchange_edit(h, r["apply_swap"], r["idx"], r["cnt"], pl.basis, pl.basis, pl.donor,
+                                 r["donor_src"], None, None, None, 1.0, ctx.w_next, ctx.eps, x)
 
     def _noise(self, h, x, ctx, r, hit, kind, sl) -> None:
         """The norm-matched controls: kind-3 rows with the SAE tables (and the clamp / steer targets, built as for

@@ -712,6 +712,26 @@ def matched_noise_edit(h, apply, idx, cnt, E, Dm, seeds, pos, val=None, bias=Non
     return h
 
 
+def interchange_edit(h, apply, idx, cnt, E, Dm, donor, src, bias=None, thr=None, pre_bias=None, alpha=1.0, w_next=None,
+                     eps=1e-6, x_next=None, coef_out=None, dcoef_out=None):
+    """Interchange (donor-swap) intervention, in place: per flagged row with donor row ``d = donor[src[row]]``
+    (``donor [R, D]`` like ``h``, ``src [rows]`` int32), ``h <- bf16(h - sum_j c_j Dm[idx_j])`` with ``c_j =
+    fl32(alpha * a_j(h)) - fl32(alpha * a_j(d))`` and ``a_j`` as in :func:`lowrank_edit`, then ``x_next = RMSNorm(h,
+    w_next)``: the selected latents (SAE tables) or subspace coordinates (``E = Dm = U``: ``h + alpha U^T U (d - h)``)
+    take the donor's values and everything else stays.  A row whose ``src`` is outside ``[0, R)`` and a row whose
+    ``c_j`` are all zero (its own donor, say) keep ``h`` and ``x_next`` bit for bit; a donor on which every selected
+    ``a_j`` is zero gives :func:`lowrank_edit`'s bits, and any donor gives :func:`latent_affine_edit`'s with ``val =
+    alpha * a(d)`` (the same device code, csrc/sae.hip).  The terms are added in slot order in fp32, so a row's bits
+    do not depend on its batch.  ``coef_out`` receives ``a_j(h)``, ``dcoef_out`` ``a_j(d)``."""
+    if h.is_cuda:
+        _k().interchange_edit(h, x_next, apply, idx, cnt, E, Dm, donor, src, bias, thr, pre_bias, float(alpha), w_next,
+                              float(eps), coef_out, dcoef_out)
+        return h
+    ref.interchange_edit(h, apply, idx, cnt, E, Dm, donor, src, bias, thr, pre_bias, alpha, w_next, eps, x_next,
+                         coef_out, dcoef_out)
+    return h
+
+
 def sae_splice_edit(h, apply, acts, idx, cnt, Wdec, b_dec=None, alpha=1.0, w_next=None, eps=1e-6, x_next=None,
                     src_row=None):
     """Reconstruct-mode SAE ablation, in place: per flagged row ``h <- bf16(b_dec + sum_{a_j != 0, ascending j}

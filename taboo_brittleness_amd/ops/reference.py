@@ -356,6 +356,52 @@ def latent_affine_edit(h: torch.Tensor, apply: torch.Tensor, idx: torch.Tensor, 
             x_next.view(-1, D)[r] = rmsnorm(hv[r:r + 1], w_next, eps)[0]
 
 
+def interchange_edit(h: torch.Tensor, apply: torch.Tensor, idx: torch.Tensor, cnt: torch.Tensor, E: torch.Tensor,
+                     Dm: torch.Tensor, donor: torch.Tensor, src: torch.Tensor, bias=None, thr=None, pre_bias=None,
+                     alpha: float = 1.0, w_next: Optional[torch.Tensor] = None, eps: float = 1e-6,
+                     x_next: Optional[torch.Tensor] = None, coef_out: Optional[torch.Tensor] = None,
+                     dcoef_out: Optional[torch.Tensor] = None) -> None:
+    """``lowrank_edit`` against a donor row ``d = donor[src[row]]`` (``h`` and ``donor`` of one dtype): ``h -= sum_j
+    c_j Dm[idx_j]`` with ``c_j = fl32(alpha * a_j(h)) - fl32(alpha * a_j(d))``, ``a_j`` as in :func:`lowrank_edit`.
+    Rows whose ``src`` is outside the donor table and rows whose ``c_j`` are all zero are left untouched.  The result
+    is rounded to bf16 only where ``h`` is bf16, so fp32 rows show the edit itself."""
+    if donor.dtype != h.dtype:
+        raise ValueError(f"interchange_edit: h is {h.dtype}, donor is {donor.dtype}")
+    D = h.shape[-1]
+    hv = h.view(-1, D)
+    dv = donor.view(-1, D)
+    M = hv.shape[0]
+    mmax = idx.numel() // M
+    iv = idx.view(M, mmax)
+
+    def acts(row, sel):
+        xb = row - pre_bias.float() if pre_bias is not None else row
+        pre = E[sel].float() @ xb
+        if bias is not None:
+            pre = pre + bias.float()[sel]
+        return torch.where(pre > thr.float()[sel], pre, torch.zeros_like(pre)) if thr is not None else pre
+
+    for r in torch.nonzero(apply.view(-1).bool()).flatten().tolist():
+        sr = int(src.view(-1)[r])
+        if sr < 0 or sr >= dv.shape[0]:
+            continue                      # no donor row for this flag
+        m = max(0, min(int(cnt.view(-1)[r]), mmax, 256))
+        sel = iv[r, :m].long()
+        x = hv[r].float()
+        a, ad = acts(x, sel), acts(dv[sr].float(), sel)
+        if coef_out is not None:
+            coef_out.view(M, mmax)[r, :m] = a
+        if dcoef_out is not None:
+            dcoef_out.view(M, mmax)[r, :m] = ad
+        c = alpha * a - alpha * ad        # both products rounded to fp32 first, as in latent_affine_edit
+        if not bool((c != 0).any()):
+            continue                      # all-zero edit: an exact no-op (h and x_next untouched)
+        newx = x - c @ Dm[sel].float()
+        hv[r] = (rbf(newx) if h.dtype == torch.bfloat16 else newx).to(h.dtype)
+        if x_next is not None and w_next is not None:
+            x_next.view(-1, D)[r] = rmsnorm(hv[r:r + 1], w_next, eps)[0]
+
+
 def matched_noise_edit(h: torch.Tensor, apply: torch.Tensor, idx: torch.Tensor, cnt: torch.Tensor, E: torch.Tensor,
                        Dm: torch.Tensor, seeds: torch.Tensor, pos: torch.Tensor, val: Optional[torch.Tensor] = None,
                        bias=None, thr=None, pre_bias=None, alpha: float = 1.0,

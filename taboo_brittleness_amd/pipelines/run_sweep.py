@@ -9,8 +9,8 @@ Stages (EP:112-160):
    on its owner group;
 3. per-rank batched execution, results all-gathered to rank 0;
 4. rank 0 writes ``sweep_cells.jsonl``, ``sweep_summary.json`` (curves with 95%
-   bootstrap CIs) and ``sweep_curves.csv``; atomic writes so a killed run never
-   leaves a half-written result (resume = rerun; finished shards are skipped).
+   bootstrap CIs) and ``sweep_curves.csv`` (plus ``swap_curves.csv`` when swap methods ran); atomic writes so a
+   killed run never leaves a half-written result (resume = rerun; finished shards are skipped).
 """
 from __future__ import annotations
 
@@ -25,7 +25,8 @@ from ..config import Config
 from ..parallel import dist as D
 from ..utils.io import atomic_write_json, atomic_write_text
 from .factory import build_stack
-from .sweep import METHODS, NOISE_METHODS, SweepRunner, summarize_cells
+from .sweep import METHODS, NOISE_METHODS, SWAP_METHODS, SweepRunner, summarize_cells
+from .sweep_types import check_swap_donor
 
 
 def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info: Optional[D.DistInfo] = None,
@@ -36,6 +37,16 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
     # an unknown mode (or a steer run that adds nothing) fails before anything is built
     check_mode(cfg.intervention.ablation_mode, cfg.intervention.clamp_value)
     check_latent_score(cfg.intervention.latent_score)
+    swap = any(m in SWAP_METHODS for m in methods)
+    if swap:
+        check_swap_donor(cfg.intervention.swap_donor)
+        if cfg.intervention.measure_forcing:
+            raise ValueError("measure_forcing cannot be combined with the swap methods: a forcing edit acts at every "
+                             "position, where no per-spike donor row exists")
+        if any(m.startswith("sae") for m in methods if m in SWAP_METHODS) and \
+                cfg.intervention.ablation_mode != "error_preserving":
+            raise ValueError(f"sae_swap / sae_swap_random are defined for ablation_mode = error_preserving only, not "
+                             f"{cfg.intervention.ablation_mode!r}")
     info = info or D.init_distributed(cfg.parallel.backend, cfg.runtime.device)
     tp_ctx, dp_rank, dp_size = None, info.rank, info.world
     if cfg.parallel.tp > 1:
@@ -55,7 +66,7 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
                                          (tp_graphs == "auto" and getattr(tp_ctx, "p2p", None) is not None))
     runner = SweepRunner(cfg, model, tok, sae, batch=B, device=info.device, layer=stack.layer,
                          use_graphs=graphs, kv_pairs=n_pairs + 1)
-    pairs = runner.build_pairs(cfg.words, cfg.prompts)
+    pairs = runner.build_pairs(cfg.words, cfg.prompts, methods)
     # work placement by PAIR (the reference's unit of work, `src/run_generation.py:155-156`): a pair's baseline
     # and all of its cells run on one DP group, so every reuse level that works within a pair (prefix-trie
     # decode groups, lens row dedup, the pair's KV / residual prefix) is as large as on one GPU
@@ -144,6 +155,9 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
             summary["config"]["latent_score"] = runner.latent_score
         if any(m in NOISE_METHODS for m in methods):
             summary["config"]["noise_trials"] = cfg.intervention.noise_trials
+        if swap:
+            summary["config"]["swap_donor"] = runner.swap_donor
+            summary["swap_skipped"] = [{"word": w, "prompt_idx": i} for w, i in runner.swap_skipped]
         if forcing is not None:
             summary["forcing"] = forcing
         os.makedirs(out_dir, exist_ok=True)
@@ -158,6 +172,17 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
                 c["p_secret_mean"]["hi"], c["delta_p_secret"]["mean"], c["delta_nll"]["mean"], c["leak_rate"],
                 ll.get("prompt_accuracy", ""), ll.get("any_pass", ""), ll.get("global_majority_vote", "")]))
         atomic_write_text(os.path.join(out_dir, "sweep_curves.csv"), "\n".join(lines) + "\n")
+        sw = [c for c in summary["curves"] if "p_donor_mean" in c]
+        if sw:
+            sl = ["method,budget,n,p_secret_mean,delta_p,p_donor_mean,p_donor_lo,p_donor_hi,delta_p_donor,"
+                  "delta_p_donor_lo,delta_p_donor_hi,donor_leak_rate,donor_topk_rate"]
+            for c in sw:
+                sl.append(",".join(str(x) for x in [
+                    c["method"], c["budget"], c["n"], c["p_secret_mean"]["mean"], c["delta_p_secret"]["mean"],
+                    c["p_donor_mean"]["mean"], c["p_donor_mean"]["lo"], c["p_donor_mean"]["hi"],
+                    c["delta_p_donor"]["mean"], c["delta_p_donor"]["lo"], c["delta_p_donor"]["hi"],
+                    c["donor_leak_rate"], c["donor_topk_rate"]]))
+            atomic_write_text(os.path.join(out_dir, "swap_curves.csv"), "\n".join(sl) + "\n")
         if summary.get("forcing"):
             fl = ["method,budget,n_settings,forcing_success,delta_vs_unedited"]
             fl += [f"{c['method']},{c['budget']},{c['n_settings']},{c['success_rate']},{c['delta']}"

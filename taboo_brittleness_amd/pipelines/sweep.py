@@ -52,6 +52,18 @@ too, so the no-op spike skip is off (every cell's tail starts at its pair's firs
 not built); every other level stays on and exact, the edit being a pure per-row function of the very rows the tail
 feeds.
 
+The swap methods (``SWAP_METHODS``: ``sae_swap``, ``sae_swap_random``, ``proj_swap``, ``proj_swap_random``; opt-in) are
+*interchange interventions* (interp/edits.py, ``ops.interchange_edit``): at the pair's spikes the selected latents or
+subspace coordinates take the values they have in a *donor* pair's residuals -- the next word's pair with the same
+prompt, or the same word's next prompt (``intervention.swap_donor``).  The donor rows of a batch live in a
+``[B * K, D]`` table of the edit plan, refilled on the device from the donor pairs' kept residuals.  A swap edit is
+almost never a no-op, so the no-op spike skip is off for these cells; every other reuse level stays on and exact (the
+edit is a pure per-row function of the tail's rows and of constant donor rows).  Their records also report the donor's
+secret (``p_donor_*``, ``donor_leak``, ``donor_in_topk``); for that, every pair of a run with swap methods tracks the
+other words' secret ids after its decoys (:meth:`SweepRunner.build_pairs`).  With one weight set for all words (the
+offline random-init default) two words with the same prompt generate the same hint, so a ``next_word`` donor row can
+coincide with the target's row where their spikes coincide: that spike is an exact no-op of the kernel.
+
 ``intervention.latent_score = effect_lens | attr_model`` changes only how ``Pair.targeted`` is ranked
 (:meth:`SweepRunner._causal_scores`: the effect of ablating each active latent alone at the spikes on the secret's
 lens logit, or its first-order attribution to the model's own logit); cells, seeds, random pools and every reuse
@@ -83,10 +95,11 @@ from ..runtime.generation import Generator
 from .sweep_decode import DecodeMixin
 from .sweep_plan import PlanMixin
 from .sweep_readout import ReadoutMixin
-from .sweep_types import METHODS, NOISE_METHODS, Cell, NextBatch, Pair, _Carry, _Deferred
+from .sweep_types import (METHODS, NOISE_METHODS, SWAP_METHODS, Cell, NextBatch, Pair, _Carry, _Deferred,
+                          check_swap_donor)
 
-__all__ = ["METHODS", "NOISE_METHODS", "Pair", "Cell", "NextBatch", "SweepRunner", "word_targeted_latents",
-           "summarize_cells"]
+__all__ = ["METHODS", "NOISE_METHODS", "SWAP_METHODS", "Pair", "Cell", "NextBatch", "SweepRunner",
+           "word_targeted_latents", "summarize_cells"]
 
 
 class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
@@ -111,6 +124,8 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
         # how sae_targeted's latents are ranked: "corr" (EP:118-124) or the causal scores "effect_lens" /
         # "attr_model" (A.latent_effects); an unknown selector raises here
         self.latent_score = A.check_latent_score(self.iv.latent_score)
+        self.swap_donor = check_swap_donor(self.iv.swap_donor)      # donor rule of the swap methods
+        self.swap_skipped: List[Tuple[str, int]] = []               # pairs the last make_cells found no donor for
         self.exclusion = exclusion
         self.use_graphs = use_graphs
         self.prefix_share = cfg.runtime.prefix_share if prefix_share is None else prefix_share
@@ -158,17 +173,29 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
         self._drain_batch = True
         self._with_basis = True
         self._with_noise = (False, False)             # the persistent plan has the (sae_noise, proj_noise) paths
+        self._with_swap = (False, False)              # ... the (sae_swap*, proj_swap*) paths and the donor table
+        self._run_pairs: Sequence[Pair] = ()          # the pairs of the running call (Cell.donor indexes them)
 
     # ----------------------------------------------------------------- pairs
-    def build_pairs(self, words: Sequence[str], prompts: Sequence[str]) -> List[Pair]:
+    def build_pairs(self, words: Sequence[str], prompts: Sequence[str], methods: Sequence[str] = ()) -> List[Pair]:
+        """``methods``: the methods the pairs' cells will run.  With a swap method among them every pair also tracks
+        the space-form secret id of every other word, after its decoys (``Pair.extra``), so that its baseline and
+        its cells read out a donor's secret; without one the pairs are what they always were."""
         pairs = []
+        swap = any(m in SWAP_METHODS for m in methods)
         for w in words:
             forms = list(self.cfg.word_plurals.get(w, [w]))
             track = [secret_token_id(self.tok, w, "space"), secret_token_id(self.tok, w, "bare")]
             for d in self.iv.decoys.get(w, []):
                 track.append(secret_token_id(self.tok, d, "space"))
+            extra = {}
+            if swap:
+                for w2 in words:
+                    if w2 != w and w2 not in extra:
+                        extra[w2] = len(track)
+                        track.append(secret_token_id(self.tok, w2, "space"))
             for i, p in enumerate(prompts):
-                pairs.append(Pair(w, i, p, hint_prompt_ids(self.tok, p), forms, track))
+                pairs.append(Pair(w, i, p, hint_prompt_ids(self.tok, p), forms, track, extra=dict(extra)))
         return pairs
 
     def _ensure_gen(self, S: int) -> Generator:
@@ -280,24 +307,29 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
         self._drain = drain
         self._pre_plan = plan
         self._running_cells = cells
+        self._run_pairs = pairs
         ride = list(ride_along)
         if not cells and not ride:
             return []
         gen = self._ensure_gen(self._S_needed(list(pairs) + ride))
-        bases = self._bases(pairs) if any(c.kind == "proj" for c in cells) else {}
+        bases = self._bases(pairs, self._needs_all_pool(cells)) if any(c.kind == "proj" for c in cells) else {}
         if self._plan is None:
             self._with_basis = any(c.kind == "proj" for c in cells) or bool(self.iv.ranks and not cells)
         elif any(c.kind == "proj" for c in cells) and self._plan.basis is None:
             self._plan = None                                # plan layout changes: rebuild + recapture
             self.gen.invalidate_graph()
             self._with_basis = True
-        noise = self._noise_kinds(cells)
+        noise, swap = self._noise_kinds(cells), self._swap_kinds(cells)
+        if any(swap) and self.carry_rows:
+            raise ValueError("swap cells do not support the decode-tail carry-over (carry_rows > 0): a carried cell's "
+                             "donor rows would have to move with it")
         if self._plan is None:
-            self._with_noise = noise
-        elif any(w and not h for w, h in zip(noise, self._plan.has_noise)):
-            # first noise cells of this runner: the plan gains the noise path (rebuild + recapture, as for a basis)
-            assert not self._carry, "carried cells live in the old plan: drain before the first noise cells"
+            self._with_noise, self._with_swap = noise, swap
+        elif any(w and not h for w, h in zip(noise + swap, self._plan.has_noise + self._plan.has_swap)):
+            # first noise / swap cells of this runner: the plan gains that path (rebuild + recapture, as for a basis)
+            assert not self._carry, "carried cells live in the old plan: drain before the first noise / swap cells"
             self._with_noise = tuple(w or h for w, h in zip(noise, self._plan.has_noise))
+            self._with_swap = tuple(w or h for w, h in zip(swap, self._plan.has_swap))
             self._with_basis = self._plan.basis is not None
             self._plan = None
             self.gen.invalidate_graph()
@@ -389,5 +421,10 @@ def summarize_cells(results: Sequence[dict], words: Sequence[str], word_plurals:
         ent["ll_topk"] = {k: float(np.mean([m[k] for m in per_trial])) for k in per_trial[0]} if per_trial else {}
         if meth in NOISE_METHODS:                # how far the control (= its targeted twin) moved the stream
             ent["edit_norm"] = float(np.mean([r["edit_norm"] for r in rs]))
+        if meth in SWAP_METHODS:                 # what the transplant did to the donor's secret
+            ent["p_donor_mean"] = bootstrap_ci([r["p_donor_mean"] for r in rs], seed=bud + 2)
+            ent["delta_p_donor"] = bootstrap_ci([r["delta_p_donor"] for r in rs], seed=bud + 3)
+            ent["donor_leak_rate"] = float(np.mean([r["donor_leak"] for r in rs]))
+            ent["donor_topk_rate"] = float(np.mean([r["donor_in_topk"] for r in rs]))
         curves.append(ent)
     return {"curves": curves}

@@ -15,7 +15,7 @@ import torch
 from .. import ops
 from ..interp import analysis as A
 from ..interp.edits import EditHook, EditPlan
-from .sweep_types import METHODS, NOISE_METHODS, SPLICE_METHOD, Cell, NextBatch, Pair, _h2d
+from .sweep_types import METHODS, NOISE_METHODS, SPLICE_METHOD, SWAP_METHODS, Cell, NextBatch, Pair, _h2d
 
 
 class PlanMixin:
@@ -209,6 +209,48 @@ class PlanMixin:
         ms = {c.method for c in cells}
         return ("sae_noise" in ms, "proj_noise" in ms)
 
+    @staticmethod
+    def _swap_kinds(cells: Sequence[Cell]) -> Tuple[bool, bool]:
+        ms = {c.method for c in cells}
+        return (bool(ms & {"sae_swap", "sae_swap_random"}), bool(ms & {"proj_swap", "proj_swap_random"}))
+
+    def _needs_all_pool(self, cells: Sequence[Cell]) -> bool:
+        """``proj_swap`` reads the basis pooled over all pairs, whatever ``pca_pool`` says: between-word directions
+        are what a swap must carry."""
+        return self.iv.pca_pool == "word" and any(c.method == "proj_swap" for c in cells)
+
+    @staticmethod
+    def _donor_eligible(q: Pair) -> bool:
+        return q.resid is not None and q.resid.shape[0] > 0 and bool(q.spikes_rel)
+
+    def swap_donors(self, pairs: Sequence[Pair]) -> List[int]:
+        """Per pair, the index of its donor among ``pairs`` (-1: none) under ``intervention.swap_donor``:
+        ``next_word`` -- the pair of the next word in ``cfg.words`` order (cyclic, own word skipped) with the same
+        prompt index; ``next_prompt`` -- the same word's next prompt index (cyclic).  A candidate without a baseline
+        or without spikes is skipped and the next one is tried."""
+        at: Dict[tuple, int] = {}
+        for i, q in enumerate(pairs):
+            at.setdefault((q.word, q.pidx, q.rep), i)
+            at.setdefault((q.word, q.pidx), i)
+        words = list(self.cfg.words) + sorted({q.word for q in pairs} - set(self.cfg.words))
+        out = []
+        for p in pairs:
+            if self.swap_donor == "next_word":
+                w0 = words.index(p.word)
+                cand = [(words[(w0 + k) % len(words)], p.pidx) for k in range(1, len(words))]
+            else:
+                idxs = sorted({q.pidx for q in pairs if q.word == p.word})
+                i0 = idxs.index(p.pidx)
+                cand = [(p.word, idxs[(i0 + k) % len(idxs)]) for k in range(1, len(idxs))]
+            d = -1
+            for w, i in cand:
+                j = at.get((w, i, p.rep), at.get((w, i), -1))
+                if j >= 0 and pairs[j] is not p and self._donor_eligible(pairs[j]):
+                    d = j
+                    break
+            out.append(d)
+        return out
+
     @torch.no_grad()
     def _edit_norms(self, pairs: Sequence[Pair], cells: Sequence[Cell], bases: Dict[str, torch.Tensor]) -> None:
         """How far the norm-matched controls move the stream: per (pair, noise method, budget), the mean over the
@@ -288,16 +330,31 @@ class PlanMixin:
         if "sae_noise" in methods and self.ablation_mode == "reconstruct":
             raise ValueError("sae_noise has no meaning under ablation_mode = reconstruct: the splice replaces the "
                              "residual, so there is no added delta whose norm could be matched")
+        swap = [m for m in methods if m in SWAP_METHODS]
+        donors: List[int] = []
+        if swap:
+            if any(m.startswith("sae") for m in swap) and self.ablation_mode != "error_preserving":
+                raise ValueError(f"sae_swap / sae_swap_random are defined for ablation_mode = error_preserving only, "
+                                 f"not {self.ablation_mode!r}")
+            if any(p.extra is None or not all(q.word == p.word or q.word in p.extra for q in pairs) for p in pairs):
+                raise ValueError("swap methods need pairs that track the other words' secrets: "
+                                 "build_pairs(words, prompts, methods)")
+            donors = self.swap_donors(pairs)
+            self.swap_skipped = [(p.word, p.pidx) for p, d in zip(pairs, donors) if d < 0]
         for pi, p in enumerate(pairs):
             for meth in methods:
                 if meth == SPLICE_METHOD:
                     continue                         # added below, once per pair, in reconstruct mode only
+                if meth in SWAP_METHODS and donors[pi] < 0:
+                    continue                         # no eligible donor: no swap cells (swap_skipped)
                 if meth.startswith("sae"):
                     if self.sae is None:
                         continue
-                    budgets, trials = self.iv.budgets, (1 if meth == "sae_targeted" else self.iv.random_trials)
+                    budgets = self.iv.budgets
+                    trials = 1 if meth in ("sae_targeted", "sae_swap") else self.iv.random_trials
                 else:
-                    budgets, trials = self.iv.ranks, (1 if meth == "proj_targeted" else self.iv.proj_random_trials)
+                    budgets = self.iv.ranks
+                    trials = 1 if meth in ("proj_targeted", "proj_swap") else self.iv.proj_random_trials
                 if meth in NOISE_METHODS:
                     trials = self.iv.noise_trials
                 for bud in budgets:
@@ -305,17 +362,19 @@ class PlanMixin:
                         # replicate 0 keeps the plain key, so sweeps seeded before replicates existed reproduce;
                         # a replicate > 0 (the bench's repeated pairs) draws its own random latent sets / subspaces
                         key = (base, p.word, p.pidx, meth, bud, t) + ((p.rep,) if p.rep else ())
-                        cells.append(Cell(pi, meth, int(bud), t, A.cell_seed(*key)))
+                        cells.append(Cell(pi, meth, int(bud), t, A.cell_seed(*key),
+                                          donors[pi] if meth in SWAP_METHODS else -1))
             if self.ablation_mode == "reconstruct" and self.sae is not None and \
                     any(meth.startswith("sae") for meth in methods):
                 key = (base, p.word, p.pidx, SPLICE_METHOD, 0, 0) + ((p.rep,) if p.rep else ())
                 cells.append(Cell(pi, SPLICE_METHOD, 0, 0, A.cell_seed(*key)))      # the pure-splice control
         return cells
 
-    def _bases(self, pairs: Sequence[Pair]) -> Dict[str, torch.Tensor]:
+    def _bases(self, pairs: Sequence[Pair], with_all: bool = False) -> Dict[str, torch.Tensor]:
         """Targeted secret subspaces pooled per word (or across all pairs): PCA of the spike residuals
         (EP:144-146) or, with ``intervention.subspace = grad_lens | grad_model``, the top singular directions of
-        the secret-logit gradients at the spikes (EP:146's alternative; interp/gradient.py)."""
+        the secret-logit gradients at the spikes (EP:146's alternative; interp/gradient.py).  ``with_all``: under
+        ``pca_pool = word`` also the ``__all__`` pool (``proj_swap``)."""
         from ..interp import gradient as GR
 
         rmax = max(self.iv.ranks) if self.iv.ranks else 1
@@ -325,15 +384,17 @@ class PlanMixin:
         # the bases depend only on the pairs' kept baseline residuals (identity-keyed: a re-run baseline makes a
         # new tensor) and the subspace settings; run_sweep passes every pair on every chunk and the staged plan
         # asks again, so the gradient forward/backward passes run once per pair set
-        ckey = (mode, self.iv.pca_pool, rmax, tuple((id(p), id(p.resid), tuple(p.spikes_rel or ())) for p in pairs))
+        ckey = (mode, self.iv.pca_pool, bool(with_all), rmax,
+                tuple((id(p), id(p.resid), tuple(p.spikes_rel or ())) for p in pairs))
         cache = getattr(self, "_bases_cache", None)
         if cache is not None and cache[0] == ckey:
             return cache[1]
-        out = self._bases_compute(pairs, mode, rmax)
+        out = self._bases_compute(pairs, mode, rmax, with_all)
         self._bases_cache = (ckey, out, [p.resid for p in pairs])   # refs held: the ids cannot be reused
         return out
 
-    def _bases_compute(self, pairs: Sequence[Pair], mode: str, rmax: int) -> Dict[str, torch.Tensor]:
+    def _bases_compute(self, pairs: Sequence[Pair], mode: str, rmax: int,
+                       with_all: bool = False) -> Dict[str, torch.Tensor]:
         from ..interp import gradient as GR
 
         groups: Dict[str, List[torch.Tensor]] = {}
@@ -353,6 +414,8 @@ class PlanMixin:
                 seq = torch.cat([pre, p.resid], 0)
                 sp = [p.plen + t for t in p.spikes_rel]
                 groups.setdefault(key, []).append(GR.model_gradients(self.m, seq, self.layer, sp, p.track[:1]))
+            if with_all and key != "__all__":
+                groups.setdefault("__all__", []).append(groups[key][-1])
         if mode == "pca":
             return {k: A.secret_subspace(torch.cat(v, 0), rmax) for k, v in groups.items()}
         return {k: GR.gradient_subspace(torch.cat(v, 0), rmax, seed=A.cell_seed("grad", k, rmax))
@@ -364,6 +427,8 @@ class PlanMixin:
         projection basis rows to upload (row ``i * rmax + j`` = j-th direction of proj cell ``i``)."""
         K = self.iv.spikes_k
         mmax = max([max(self.iv.budgets or [1]), max(self.iv.ranks or [1])])
+        if self._with_swap[0] or self._swap_kinds(cells)[0]:
+            mmax = max(mmax, 2 * max(self.iv.budgets or [1]))      # sae_swap: the target's and the donor's latents
         rmax = max(self.iv.ranks) if self.iv.ranks else 1
         B = self.B
         sp = np.full((B, K), -1, dtype=np.int32)
@@ -371,6 +436,9 @@ class PlanMixin:
         cn = np.zeros(B, dtype=np.int32)
         kd = np.zeros(B, dtype=np.int8)
         sd = np.zeros(B, dtype=np.int64)                   # noise streams of the sae_noise / proj_noise rows
+        db = np.full(B, -1, dtype=np.int32)                # first donor-table row of the swap rows (row b * K + k)
+        dn_dst: List[int] = []                             # donor table: rows to fill, and (donor pair, response
+        dn_src: List[Tuple[int, int]] = []                 # index) of the residual that goes there
         tgt: Dict[str, Tuple[List[int], List[int]]] = {}   # pooled basis -> (table rows, its rows)
         rproj: Tuple[List[int], List[int], List[int]] = ([], [], [])   # random controls: (first row, rank, seed)
         by_pair: Dict[int, List[int]] = {}
@@ -383,7 +451,7 @@ class PlanMixin:
             if s_abs:
                 sp[ca, : len(s_abs)] = s_abs
             rnd = [ci for ci in cis if cells[ci].kind == "sae" and
-                   cells[ci].method not in ("sae_targeted", "sae_noise", SPLICE_METHOD)]
+                   cells[ci].method not in ("sae_targeted", "sae_noise", SPLICE_METHOD) + SWAP_METHODS]
             if rnd:
                 got = A.random_latents_batch(self.sae.d_sae, [cells[ci].budget for ci in rnd],
                                              [cells[ci].seed for ci in rnd],
@@ -393,8 +461,11 @@ class PlanMixin:
                     cn[ci] = len(g)
                 kd[rnd] = 1
             tg = np.asarray(p.targeted[:mmax], dtype=np.int32)
+            self._plan_swap_rows(cells, cis, p, pairs, K, rmax, bases, ix, cn, kd, db, dn_dst, dn_src, tgt, rproj)
             for ci in cis:
                 c = cells[ci]
+                if c.method in SWAP_METHODS:
+                    continue
                 if c.kind == "sae":
                     if c.method in ("sae_targeted", "sae_noise"):     # the control takes the targeted cell's latents
                         n = min(c.budget, tg.size)
@@ -431,9 +502,53 @@ class PlanMixin:
                      "bases": {k: bases[k] for k in tgt},
                      "rnd": tuple(np.asarray(v, t)[lpt] for v, t in zip(rproj, (np.int64, np.int32, np.int64)))}
         plan = {"spikes": sp, "kind": kd, "idx": ix, "cnt": cn, "seeds": sd, "basis": basis, "rows": B * rmax,
-                "rmax": rmax,
+                "rmax": rmax, "donor_base": db,
+                "donor": (np.asarray(dn_dst, np.int64), dn_src, pairs) if dn_dst else None,
                 "f": self._effective_first_edit(cells, pairs, by_pair, kd, ix, cn)}
         return self._plan_add_carry(plan) if with_carry else plan
+
+    def _plan_swap_rows(self, cells, cis, p, pairs, K, rmax, bases, ix, cn, kd, db, dn_dst, dn_src, tgt, rproj) -> None:
+        """The swap cells of pair ``p`` (plan rows ``cis``): their selected sets, kinds 5 / 6, and the donor rows of
+        their spikes -- plan row ``ci`` reads donor-table rows ``ci * K + k``, the donor's residual at its
+        ``k mod n``-th spike (``n`` = the donor's spike count)."""
+        for ci in cis:
+            c = cells[ci]
+            if c.method not in SWAP_METHODS:
+                continue
+            q = pairs[c.donor]
+            qs = [t for t in q.spikes_rel if 0 <= t < q.resid.shape[0]]
+            assert qs, "swap cell whose donor has no spikes (make_cells skips those pairs)"
+            db[ci] = ci * K
+            for k in range(len(p.spikes_abs[:K])):
+                dn_dst.append(ci * K + k)
+                dn_src.append((c.donor, qs[k % len(qs)]))
+            if c.method == "sae_swap":
+                lat = list(dict.fromkeys(list(p.targeted[: c.budget]) + list(q.targeted[: c.budget])))
+            elif c.method == "sae_swap_random":
+                excl = list(dict.fromkeys(list(p.targeted[: c.budget]) + list(q.targeted[: c.budget])))
+                own = A.random_latents(self.sae.d_sae, c.budget, c.seed, exclude=excl, pool=p.active_pool)
+                oth = A.random_latents(self.sae.d_sae, c.budget, A.cell_seed(c.seed, "donor"), exclude=excl,
+                                       pool=q.active_pool)
+                lat = list(dict.fromkeys(list(own) + list(oth)))
+            if c.kind == "sae":
+                lat = lat[: ix.shape[1]]
+                ix[ci, : len(lat)] = lat
+                cn[ci] = len(lat)
+                kd[ci] = 5
+                continue
+            if c.method == "proj_swap":
+                r = min(c.budget, int(bases["__all__"].shape[0]))
+                dst, src = tgt.setdefault("__all__", ([], []))
+                dst.extend(range(ci * rmax, ci * rmax + r))
+                src.extend(range(r))
+            else:
+                r = c.budget
+                rproj[0].append(ci * rmax)
+                rproj[1].append(r)
+                rproj[2].append(c.seed)
+            ix[ci, :r] = np.arange(ci * rmax, ci * rmax + r)
+            cn[ci] = r
+            kd[ci] = 6
 
     def _sae_key(self) -> Optional[tuple]:
         """Identity + in-place version of the SAE tensors an edit's coefficients depend on: an activity table
@@ -492,9 +607,10 @@ class PlanMixin:
         :meth:`run_cells` / :meth:`run_cells_async` as ``prefetched``; ``None`` if it cannot apply."""
         if not pairs or any(p.resid is None for p in pairs):
             return None
-        if any(not m.startswith("sae") for m in methods):
+        if any(not m.startswith("sae") or m in SWAP_METHODS for m in methods):
             # projection cells: their plan needs the pooled PCA bases (device work, main thread); the cells are
-            # enumerated here (the random-control bases are drawn on the device when the plan loads)
+            # enumerated here (the random-control bases are drawn on the device when the plan loads).  Swap cells
+            # likewise: their plan reads the donor pairs' residuals
             if getattr(self, "_prefetch_pool", None) is None:
                 from concurrent.futures import ThreadPoolExecutor
 
@@ -528,13 +644,33 @@ class PlanMixin:
             # the noise paths exist only in a plan built for a call with noise cells (self._with_noise): every other
             # sweep runs the kernels it ran before
             noise = tuple(self._with_noise)
+            # likewise the swap paths and their donor table ([B * K, D], model dtype): only in a plan built for a call
+            # with swap cells
+            swap = tuple(self._with_swap)
+            donor = torch.zeros(plan["spikes"].shape[0] * plan["spikes"].shape[1], self.D, dtype=self.m.dtype,
+                                device=dev) if any(swap) else None
             self._plan = EditPlan(t(plan["spikes"]), t(plan["kind"]), t(plan["idx"]), t(plan["cnt"]), self.iv.alpha,
                                   basis, self.ablation_mode, values=values,
-                                  seeds=t(plan["seeds"]) if any(noise) else None, has_noise=noise)
+                                  seeds=t(plan["seeds"]) if any(noise) else None, has_noise=noise, donor=donor,
+                                  donor_base=t(plan["donor_base"]) if any(swap) else None, has_swap=swap)
             self._hook = EditHook(self._plan, self.sae)
         else:
-            for f in ("spikes", "kind", "idx", "cnt") + (("seeds",) if self._plan.seeds is not None else ()):
+            for f in ("spikes", "kind", "idx", "cnt") + (("seeds",) if self._plan.seeds is not None else ()) + \
+                    (("donor_base",) if self._plan.donor_base is not None else ()):
                 getattr(self._plan, f).copy_(_h2d(plan[f], dev), non_blocking=True)
+        if plan.get("donor") is not None:
+            # the donor rows of this batch's swap cells, gathered on the device from the donor pairs' kept residuals
+            assert self._plan.donor is not None, "swap cells need a plan built with a donor table"
+            dst, src, prs = plan["donor"]
+            up = lambda a: _h2d(a, dev).to(dev, non_blocking=True)   # noqa: E731
+            uniq = sorted({j for j, _ in src})
+            off, n = {}, 0
+            for j in uniq:
+                off[j] = n
+                n += int(prs[j].resid.shape[0])
+            R = torch.cat([prs[j].resid for j in uniq], 0) if len(uniq) > 1 else prs[uniq[0]].resid
+            rows = np.asarray([off[j] + t for j, t in src], np.int64)
+            self._plan.donor.index_copy_(0, up(dst), R.index_select(0, up(rows)).to(self._plan.donor.dtype))
         if plan["basis"] is not None:
             assert self._plan.basis is not None, "projection cells need a plan built with a basis table"
             pb, tab = plan["basis"], self._plan.basis
@@ -578,8 +714,12 @@ class PlanMixin:
             return
         if self._plan is None or any(w and not h for w, h in zip(self._noise_kinds(nb.cells), self._plan.has_noise)):
             return                               # the plan has no noise path yet: run_cells rebuilds it
+        if any(w and not h for w, h in zip(self._swap_kinds(nb.cells), self._plan.has_swap)):
+            return                               # likewise the swap paths
         if nb.plan is None:      # bases pooled over the call's pairs, as run_cells computes them
-            nb.plan = self._plan_for(nb.cells, nb.pairs, self._bases(nb.pairs) if proj else {}, with_carry=False)
+            nb.plan = self._plan_for(nb.cells, nb.pairs,
+                                     self._bases(nb.pairs, self._needs_all_pool(nb.cells)) if proj else {},
+                                     with_carry=False)
         plan = nb.plan
         nb.plan = plan
         if self._carry:                          # the next decode continues this batch's carried rows

@@ -15,7 +15,7 @@ from ..interp import analysis as A
 from ..interp.edits import EditHook
 from ..interp.logit_lens import excl_table, lens_packed, lens_readout, reference_exclusions, vocab_slice, vocab_topk
 from ..interp.prompts import contains_secret
-from .sweep_types import NOISE_METHODS, Cell, Pair, _h2d, _nullctx
+from .sweep_types import NOISE_METHODS, SWAP_METHODS, Cell, Pair, _h2d, _nullctx
 
 # bf16 logits per vocab-head GEMM chunk of the teacher-forced tail: 2 GB (4096 rows) measured +0.65 % over 1 GB at the
 # same 263 GB peak; 4 GB +0.3 % more but 276 GB peak (profiles/r5/bench/head_chunk/)
@@ -150,7 +150,9 @@ class ReadoutMixin:
         pr, vh, ih = (t.numpy() for t in host)
         self._tick("lens")
         cols = {"ng": ng_a, "d": d_a, "div": div, "j": j_a, "sn": sn_a, "nll": nll_a, "pos": pos,
-                "cell_of": cell_of, "host_tok": host_tok}
+                "cell_of": cell_of, "host_tok": host_tok,
+                # swap cells: their donor pairs, resolved now (the records may be built after the next call began)
+                "donors": [self._run_pairs[c.donor] if c.donor >= 0 else None for c in batch]}
         if getattr(self, "_defer", False):
             return self._records_pool().submit(self._resume_records, batch, cell_pairs, cols, pr, vh, ih, K)
         return self._resume_records(batch, cell_pairs, cols, pr, vh, ih, K)
@@ -236,9 +238,11 @@ class ReadoutMixin:
             resp = host_tok[j_a[b], :ng].tolist() if div[b] else p.resp
             topk = ih[b].tolist() if ng > 0 and vh[b] > 0 else []
             stats = (float(ps_mean[b]), float(ps_final[b]), float(ps_max[b])) if ng else (0.0, 0.0, 0.0)
-            dec = decoy[b, : len(p.track) - 2].tolist() if (decoy is not None and ng and len(p.track) > 2) else []
+            dec = decoy[b, : p.n_decoys].tolist() if (decoy is not None and ng and p.n_decoys > 0) else []
+            q = cols["donors"][b]
             results.append(self._cell_record(c, p, ng, resp, stats, dec, topk, float(cols["nll"][b]),
-                                             float(cols["sn"][b])))
+                                             float(cols["sn"][b]), q,
+                                             P3[b, :ng, p.extra.get(q.word, 0)] if q is not None else None))
         return results
 
     @torch.no_grad()
@@ -523,11 +527,16 @@ class ReadoutMixin:
                      nll_edit: float, nll_self: float) -> dict:
         ps = probs[:, 0] if probs.shape[0] else np.zeros(0, dtype=np.float32)
         stats = (float(ps.mean()), float(ps[-1]), float(ps.max())) if ps.size else (0.0, 0.0, 0.0)
-        dec = [float(x) for x in probs[:, 2:].mean(0)] if probs.shape[0] else []
-        return self._cell_record(c, p, n_gen, resp, stats, dec, topk_ids, nll_edit, nll_self)
+        dec = [float(x) for x in probs[:, 2: 2 + p.n_decoys].mean(0)] if probs.shape[0] else []
+        q = self._run_pairs[c.donor] if c.donor >= 0 else None
+        return self._cell_record(c, p, n_gen, resp, stats, dec, topk_ids, nll_edit, nll_self, q,
+                                 probs[:, p.extra.get(q.word, 0)] if q is not None else None)
 
     def _cell_record(self, c: Cell, p: Pair, n_gen: int, resp: List[int], stats: Tuple[float, float, float],
-                     decoy: List[float], topk_ids: List[int], nll_edit: float, nll_self: float) -> dict:
+                     decoy: List[float], topk_ids: List[int], nll_edit: float, nll_self: float,
+                     donor: Optional[Pair] = None, p_donor: Optional[np.ndarray] = None) -> dict:
+        """``donor`` / ``p_donor`` (swap cells only): the donor pair and the lens probability of its secret (space
+        form) over the cell's response."""
         dc = self._dec_cache
         guesses = []
         for t in topk_ids:
@@ -559,6 +568,19 @@ class ReadoutMixin:
         }
         if c.method in NOISE_METHODS:            # norm-matched controls only: the other records keep their keys
             rec["edit_norm"] = p.edit_norm[1][(c.method, c.budget)]
+        if c.method in SWAP_METHODS:             # interchange cells only: what became of the donor's secret
+            q, col = donor, p.extra.get(donor.word, 0)        # next_prompt: the donor's secret is the pair's own
+            pd = np.asarray(p_donor, dtype=np.float32)
+            base = float(p.track_probs[:, col].mean()) if p.track_probs is not None and p.track_probs.shape[0] else 0.0
+            mean = float(pd.mean()) if pd.size else 0.0
+            rec.update({
+                "donor_word": q.word, "donor_prompt_idx": q.pidx,
+                "p_donor_mean": mean, "p_donor_final": float(pd[-1]) if pd.size else 0.0,
+                "p_donor_max": float(pd.max()) if pd.size else 0.0,
+                "delta_p_donor": mean - base,       # against the target pair's own baseline
+                "donor_leak": contains_secret(self.tok.decode(resp), q.forms),
+                "donor_in_topk": int(q.track[0]) in [int(t) for t in topk_ids],
+            })
         return rec
 
     def _nll_ws(self, M: int, key: int = 0):

@@ -4,7 +4,7 @@ intervention setting), a decode-tail carry record, the prefetched next batch, pi
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import List, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -18,6 +18,18 @@ SPLICE_METHOD = "sae_splice"
 # budget / rank, whose residual moves exactly as far at the same positions but along a seeded random direction
 # (ops.matched_noise_edit); ``intervention.noise_trials`` cells per budget / rank
 NOISE_METHODS = ("sae_noise", "proj_noise")
+# interchange (donor-swap) interventions (opt-in, never part of METHODS): at the pair's spikes the selected latents
+# (``sae_swap``: the target's and the donor's targeted latents; ``sae_swap_random``: random active ones) or subspace
+# coordinates (``proj_swap``: the basis pooled over all pairs; ``proj_swap_random``: a random one) take the values they
+# have in a donor pair's residuals (ops.interchange_edit); the donor is chosen by ``intervention.swap_donor``
+SWAP_METHODS = ("sae_swap", "sae_swap_random", "proj_swap", "proj_swap_random")
+SWAP_DONORS = ("next_word", "next_prompt")
+
+
+def check_swap_donor(rule: str) -> str:
+    if rule not in SWAP_DONORS:
+        raise ValueError(f"intervention.swap_donor must be one of {', '.join(SWAP_DONORS)}, not {rule!r}")
+    return rule
 
 
 @dataclass
@@ -63,6 +75,13 @@ class Pair:
     # norm-matched controls only: (the baseline residuals the figures were taken from, {(method, budget): mean over
     # the spikes of |targeted delta|_2 / |h|_2}) -- SweepRunner._edit_norms
     edit_norm: Optional[tuple] = None
+    # swap methods only: word -> column of ``track`` holding that other word's secret id (space form), appended after
+    # the decoys (SweepRunner.build_pairs); the decoy readouts stop before these columns
+    extra: Dict[str, int] = field(default_factory=dict)
+
+    @property
+    def n_decoys(self) -> int:
+        return len(self.track) - 2 - len(self.extra)
 
     @property
     def first_edit(self) -> int:
@@ -87,6 +106,7 @@ class Cell:
     budget: int
     trial: int
     seed: int
+    donor: int = -1                        # swap methods: index of the donor pair among the call's pairs
 
     @property
     def kind(self) -> str:

@@ -5,6 +5,8 @@
 * ``fig2_lowrank.png`` — the same for the low-rank projection vs rank r;
 * ``fig3_content_vs_inhibition.png`` — Δ secret probability vs Δ inhibition
   (token-forcing success when measured, else leak rate), one point per setting;
+* ``fig4_interchange.png`` — interchange (donor-swap) interventions, only for sweeps that ran them: the
+  target's and the donor's secret probability vs budget / rank, targeted swap vs random swap;
 * ``table_baselines.csv`` — LL-Top-k / SAE-Top-k / token forcing rows with
   Pass@10, Majority@10, Accuracy.
 """
@@ -127,6 +129,37 @@ def intervention_curves(summary: Dict, kind: str, path: str) -> None:
     plt.close(fig)
 
 
+def interchange_curves(summary: Dict, path: str) -> None:
+    """Interchange interventions: the target's secret probability and the donor's against budget m (SAE latents) and
+    rank r (subspace), the swap of the targeted set against the swap of a random one."""
+    curves = summary["curves"]
+    rows = [("sae", "budget m"), ("proj", "rank r")]
+    panels = [("p_secret_mean", "target: LL secret prob"), ("p_donor_mean", "donor: LL secret prob"),
+              ("delta_p_donor", "donor: Δ vs the target's baseline")]
+    fig, axes = plt.subplots(len(rows), len(panels), figsize=(5 * len(panels), 4 * len(rows)), squeeze=False)
+    for i, (kind, xlabel) in enumerate(rows):
+        for ax, (key, title) in zip(axes[i], panels):
+            for meth, col in ((f"{kind}_swap", "tab:red"), (f"{kind}_swap_random", "tab:blue")):
+                xs, ys, lo, hi = _curve(curves, meth, key)
+                if not xs:
+                    continue
+                ax.plot(xs, ys, "o-", color=col, label=meth)
+                if lo is not None:
+                    ax.fill_between(xs, lo, hi, color=col, alpha=0.2)
+            ax.set_xscale("log", base=2)
+            ax.set_title(title)
+            ax.set_xlabel(xlabel)
+        if axes[i][0].get_legend_handles_labels()[0]:
+            axes[i][0].legend()
+    donor = (summary.get("config") or {}).get("swap_donor")
+    if donor:
+        fig.suptitle(f"interchange interventions, donor: {donor}")
+    plt.tight_layout()
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    fig.savefig(path, dpi=150)
+    plt.close(fig)
+
+
 def content_vs_inhibition(summary: Dict, path: str, forcing_delta: Optional[Dict] = None) -> None:
     fig, ax = plt.subplots(figsize=(6, 5))
     for c in summary["curves"]:
@@ -173,6 +206,10 @@ def make_report(results_dir: str, out_dir: str) -> List[str]:
             if {"proj_targeted", "proj_random"} & methods:
                 p = os.path.join(out_dir, f"fig2_lowrank_{tag}.png")
                 intervention_curves(s, "proj", p)
+                made.append(p)
+            if any("p_donor_mean" in c for c in s["curves"]):      # only sweeps that ran the swap methods
+                p = os.path.join(out_dir, f"fig4_interchange_{tag}.png")
+                interchange_curves(s, p)
                 made.append(p)
             p = os.path.join(out_dir, f"fig3_content_vs_inhibition_{tag}.png")
             fd = ({f"{c['method']}:{c['budget']}": c["delta"] for c in s["forcing"]["curves"]}
