@@ -27,10 +27,15 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=None)
     ap.add_argument("--forcing", action="store_true",
                     help="also measure postgame token forcing under each (method, budget) edit (EP:100-104)")
+    ap.add_argument("--output-readout", action="store_true",
+                    help="also record the model's next-token log-prob / rank of the tracked ids at every response "
+                         "position (intervention.output_readout; no fused head, TP or decode-tail carry-over)")
     args = ap.parse_args(argv)
     cfg, dev = setup(args)
     if args.forcing:
         cfg.intervention.measure_forcing = True
+    if args.output_readout:
+        cfg.intervention.output_readout = True
     info = D.init_distributed(cfg.parallel.backend, "cpu" if dev.type == "cpu" else "auto")
     out = args.out or os.path.join(cfg.data.results_dir, "sweeps", f"{args.methods}_seed{cfg.experiment.seed}")
     summary = run_sweep(cfg, out, METHOD_SETS[args.methods], info=info, batch=args.batch)

@@ -146,6 +146,11 @@ class InterventionCfg:
     # word's pair with the same prompt: does the edit carry *which* secret it is?) or "next_prompt" (the same word's
     # next prompt, the specificity control: the same secret from another context should stay readable)
     swap_donor: str = "next_word"
+    # output-side readout (opt-in): the model's own next-token log-prob and rank of the tracked ids (secret forms,
+    # decoys, a swap donor's secret) at every response position, from the vocab head's pass over the logits
+    # (ops.decode_head_track); adds the ``logp_out_*`` / ``rank_out_*`` record fields and curves.  Read by the sweep
+    # and the forcing pipelines; off: records, files and launched kernels are what they are without it.
+    output_readout: bool = False
     score_over: str = "prompt"          # "prompt" (per prompt) or "word" (average over prompts)
     # how the targeted latents are ranked: "corr" (EP:118-124: spike-mean activation x positive correlation with the
     # secret probability), or by what ablating the latent alone does at the spikes: "effect_lens" (the exact drop of

@@ -61,6 +61,13 @@ void tb_decode_head(const uint16_t* logits, const int32_t* tgt, int32_t* nxt, fl
 // false when the cap has no registered table (caller falls back)
 bool tb_decode_head_stats(const uint16_t* logits, const int32_t* tgt, int off, float* stats, int R, int V, float cap,
                           hipStream_t st);
+// decode_head plus, per row, the log-prob (capped logit - lse) of T <= 8 tracked vocab ids ([R, T] int32, -1 = empty)
+// and the rank (count of strictly greater capped logits) of the first n_rank of them.  logp / rank are [R, T], or with
+// col ([R] int64) [R, W, T] written at column min(col[r], W - 1).  0 = launched; 1 = no softcap table / cap outside
+// the f kernel's range; 2 = TB_DECODE_HEAD selects another kernel; 3 = T / n_rank / W out of range.
+int tb_decode_head_track(const uint16_t* logits, const int32_t* tgt, int32_t* nxt, float* nll_self, float* nll_tgt,
+                         const int32_t* track, int T, int n_rank, float* logp, int32_t* rank, const int64_t* col, int W,
+                         int R, int V, float cap, hipStream_t st);
 // sae.hip
 void tb_head_merge(const float* part, int npart, const int32_t* tgt, const float* tgt_logit, int32_t* nxt,
                    float* nll_self, float* nll_tgt, float* lse, int M, int V, hipStream_t st);

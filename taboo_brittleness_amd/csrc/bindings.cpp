@@ -374,6 +374,52 @@ void decode_head(torch::Tensor logits, c10::optional<torch::Tensor> tgt, torch::
                  cur_stream());
 }
 
+// decode_head + output-side readout of tracked ids (lens.hip decode_head_track_kernel).  track [R, T] int32; logp /
+// rank [R, T], or [R, W, T] with col [R] int64 (row r writes column min(col[r], W - 1)).
+void decode_head_track(torch::Tensor logits, c10::optional<torch::Tensor> tgt, torch::Tensor nxt,
+                       torch::Tensor nll_self, c10::optional<torch::Tensor> nll_tgt, torch::Tensor track, int64_t n_rank,
+                       torch::Tensor logp, torch::Tensor rank, c10::optional<torch::Tensor> col, double cap) {
+  IN_BF16(logits); IN_I32(nxt); IN_F32(nll_self); IN_I32(track); IN_F32(logp); IN_I32(rank);
+  const int V = logits.size(-1), R = logits.numel() / V;
+  TORCH_CHECK(nxt.numel() == R && nll_self.numel() == R, "decode_head_track shapes");
+  TORCH_CHECK(tgt.has_value() == nll_tgt.has_value(), "decode_head_track: tgt and nll_tgt go together");
+  TORCH_CHECK(track.dim() == 2 && track.size(0) == R, "decode_head_track: track must be [R, T]");
+  const int64_t T = track.size(1);
+  TORCH_CHECK(T >= 1 && T <= 8, "decode_head_track: 1 <= T <= 8 tracked columns, got ", T);
+  TORCH_CHECK(n_rank >= 0 && n_rank <= T, "decode_head_track: n_rank must lie in [0, T], got ", n_rank);
+  TORCH_CHECK(cap > 0, "decode_head_track needs a final softcap (0 < cap <= 40), got ", cap);
+  const int32_t* tp = nullptr;
+  float* np = nullptr;
+  if (tgt.has_value()) {
+    IN_I32((*tgt)); IN_F32((*nll_tgt));
+    TORCH_CHECK(tgt->numel() == R && nll_tgt->numel() == R, "decode_head_track teacher shapes");
+    tp = tgt->data_ptr<int32_t>();
+    np = nll_tgt->data_ptr<float>();
+  }
+  const int64_t* cp = nullptr;
+  int64_t W = 1;
+  if (col.has_value()) {
+    CHECK_DEV((*col)); CHECK_CONTIG((*col));
+    TORCH_CHECK(col->scalar_type() == at::kLong && col->numel() == R, "decode_head_track: col must be [R] int64");
+    TORCH_CHECK(logp.dim() == 3 && logp.size(0) >= R && logp.size(2) == T, "decode_head_track: logp must be [R, W, T]");
+    W = logp.size(1);
+    TORCH_CHECK(W >= 1 && rank.dim() == 3 && rank.size(0) >= R && rank.size(1) == W && rank.size(2) == T,
+                "decode_head_track: rank must be [R, W, T]");
+    cp = col->data_ptr<int64_t>();
+  } else {
+    TORCH_CHECK(logp.numel() == (int64_t)R * T && rank.numel() == (int64_t)R * T,
+                "decode_head_track: logp / rank must be [R, T]");
+  }
+  c10::DeviceGuard g(logits.device());
+  const int rc = tb_decode_head_track(cbf(logits), tp, nxt.data_ptr<int32_t>(), nll_self.data_ptr<float>(), np,
+                                      track.data_ptr<int32_t>(), (int)T, (int)n_rank, logp.data_ptr<float>(),
+                                      rank.data_ptr<int32_t>(), cp, (int)W, R, V, (float)cap, cur_stream());
+  TORCH_CHECK(rc != 1, "decode_head_track: cap ", cap, " has no registered softcap table or exceeds 40 (the tracking "
+              "head exists for the default decode_head kernel only)");
+  TORCH_CHECK(rc != 2, "decode_head_track: TB_DECODE_HEAD selects the t / c kernel, which has no tracking version");
+  TORCH_CHECK(rc == 0, "decode_head_track: bad arguments");
+}
+
 // vocab-parallel decode head (this rank's V columns of the logits): float4 stats per row for vp_head_merge; returns
 // false (nothing launched) when the cap has no registered softcap table
 bool decode_head_stats(torch::Tensor logits, c10::optional<torch::Tensor> tgt, int64_t off, torch::Tensor stats,
@@ -1215,6 +1261,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("xent_rows", &xent_rows);
   m.def("decode_head", &decode_head);
   m.def("decode_head_stats", &decode_head_stats);
+  m.def("decode_head_track", &decode_head_track);
   m.def("register_softcap_table", &register_softcap_table);
   m.def("register_softcap_compact", &register_softcap_compact);
   m.def("softcap_compact", &softcap_compact);

@@ -14,6 +14,8 @@
 //  xent_rows      NLL of target ids under softcapped logits (fluency ΔNLL)
 //  decode_head    one pass over a decode row: greedy token (argmax_rows semantics), its NLL and
 //                 the NLL of an optional teacher target (the baseline's token at that column)
+//  decode_head_track  decode_head plus the log-prob and rank of up to 8 tracked vocab ids per row (the sweep's
+//                 output-side readout), counted in the same streamed pass
 #include "common.h"
 #include "api.h"
 #include <algorithm>
@@ -703,6 +705,166 @@ __global__ void __launch_bounds__(512) decode_head_f_kernel(const uint16_t* __re
   }
 }
 
+// decode_head_f_kernel (plain mode) plus the output-side readout of T <= DH_TRACK_MAX tracked vocab ids per row:
+// logp = capped logit - lse, and for the first n_rank <= NR columns the rank #{v : c(z[v]) > c(z[id])} (strict, so a
+// saturated tie group shares rank 0).  The ranked columns' logits are read before the stream (broadcast loads).  The
+// exp-sum and the chunk argmax are the plain kernel's statement for statement, so nxt / nll_self / nll_tgt keep its
+// bits; the compares ride along on the same capped floats.  Counting costs one VALU op per logit and ranked column:
+// v_cmp_gt_f32 against the wave-uniform threshold writes the wave's lane mask to an SGPR pair, and the population
+// count and the add run on the scalar unit beside the vector stream (no packed f32 compare exists, and packed 16-bit
+// keys would cost 1.5 ops per logit for the key before the first column).  The ballot counts a whole wave, so it is
+// used only in trips that every lane of the wave runs (the trip count is the wave's, not the lane's); the ragged
+// rest of a row -- at most UNR chunks per lane and the V % 8 tail -- is counted per lane and folded by the wave
+// reduction.  The count is an integer, so any merge order gives the same value.
+// Columns k >= n_rank inside NR compare against +inf.  With ``col`` row r writes column min(col[r], W - 1) of
+// [R, W, T] outputs (the decode's per-step columns) instead of [R, T].
+constexpr int DH_TRACK_MAX = 8;
+struct HeadTrack {
+  const int32_t* ids;   // [R, T], -1 (any id outside [0, V)) = empty column
+  float* logp;
+  int32_t* rank;
+  const int64_t* col;   // optional [R]
+  int T, n_rank, W;
+};
+
+template <int UNR, int NR>
+__global__ void __launch_bounds__(512) decode_head_track_kernel(const uint16_t* __restrict__ logits,
+                                                                const int32_t* __restrict__ tgt,
+                                                                int32_t* __restrict__ nxt, float* __restrict__ nll_self,
+                                                                float* __restrict__ nll_tgt, int R, int V,
+                                                                const uint16_t* __restrict__ tab, HeadTrack tk) {
+  __shared__ float ss[8], sv[8];
+  __shared__ int si[8];
+  __shared__ int sc[8][NR > 0 ? NR : 1];
+  extern __shared__ __attribute__((aligned(16))) uint16_t ctab_lds[];
+  const uint16_t* ct = stage_ctab(tab, ctab_lds);
+  const int nv = V >> 3;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  for (int r = blockIdx.x; r < R; r += gridDim.x) {
+    const uint16_t* row = logits + (size_t)r * V;
+    // thresholds of the ranked columns (+inf: empty or unranked, nothing counts); only these stay live over the stream
+    float thr[NR > 0 ? NR : 1];
+    int wcnt[NR > 0 ? NR : 1];   // counted by the whole wave (full trips), wave-uniform
+    int lcnt[NR > 0 ? NR : 1];   // counted by this lane alone (ragged trips)
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+      const int id = k < tk.n_rank ? tk.ids[(size_t)r * tk.T + k] : -1;
+      thr[k] = (id >= 0 && id < V) ? capped1(row[id], ct, 0.f, 1) : INFINITY;
+      wcnt[k] = 0;
+      lcnt[k] = 0;
+    }
+    float s = 0.f, bv = -INFINITY;
+    int bc = -1;
+    f2 s2 = {0.f, 0.f};
+    // the plain kernel's per-chunk statements; f stays for the counting
+    auto chunk = [&](const uint4& v, int c, float* f) {
+      capped8_tab(v, f, ct);
+      const float cm = max3_raw(max3_raw(f[0], f[1], f[2]), max3_raw(f[3], f[4], f[5]), fmax_raw(f[6], f[7]));
+#pragma unroll
+      for (int j = 0; j < 8; j += 2) {
+        const f2 y = f2{f[j], f[j + 1]} * LOG2E2;
+        s2 += f2{__builtin_amdgcn_exp2f(y.x), __builtin_amdgcn_exp2f(y.y)};
+      }
+      if (cm > bv) { bv = cm; bc = c; }
+    };
+    // stream_row's order per lane (c = tid, tid + stride, ...: the same reductions), split by the wave instead of by
+    // the lane: UNR-deep trips run while the wave's LAST lane still has all UNR chunks, so every lane is active in
+    // them and the ballot counts the whole wave; what is left (up to UNR chunks per lane, ragged over the lanes) is
+    // counted per lane
+    {
+      const uint4* p = reinterpret_cast<const uint4*>(row);
+      const int st = blockDim.x;
+      int c = threadIdx.x;
+      int cw = __builtin_amdgcn_readfirstlane(threadIdx.x) + 63;
+      for (; cw + (UNR - 1) * st < nv; cw += UNR * st, c += UNR * st) {
+        uint4 v[UNR];
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) v[u] = p[c + u * st];
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+          float f[8];
+          chunk(v[u], c + u * st, f);
+#pragma unroll
+          for (int k = 0; k < NR; ++k) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) wcnt[k] += __builtin_popcountll(__builtin_amdgcn_ballot_w64(f[j] > thr[k]));
+          }
+          if (NR > 0) __builtin_amdgcn_sched_barrier(0);   // the lane masks of one chunk, not of UNR, live in SGPRs
+        }
+      }
+      for (; c < nv; c += st) {
+        float f[8];
+        chunk(p[c], c, f);
+#pragma unroll
+        for (int k = 0; k < NR; ++k) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) lcnt[k] += f[j] > thr[k] ? 1 : 0;
+        }
+      }
+    }
+    s = s2.x + s2.y;
+    ArgBest best{bv, 0x7fffffff};
+    if (bc >= 0) {
+      float f[8];
+      capped8(reinterpret_cast<const uint4*>(row)[bc], f, ct, 0.f, 1);
+#pragma unroll
+      for (int j = 7; j >= 0; --j)
+        if (f[j] == bv) best.i = bc * 8 + j;
+    }
+    for (int c = nv * 8 + threadIdx.x; c < V; c += blockDim.x) {
+      const float x = capped1(row[c], ct, 0.f, 1);
+      s += __expf(x);
+      best = better(best, ArgBest{x, c});
+#pragma unroll
+      for (int k = 0; k < NR; ++k) lcnt[k] += x > thr[k] ? 1 : 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      s += __shfl_xor(s, o, 64);
+      ArgBest oth{__shfl_xor(best.v, o, 64), __shfl_xor(best.i, o, 64)};
+      best = better(best, oth);
+#pragma unroll
+      for (int k = 0; k < NR; ++k) lcnt[k] += __shfl_xor(lcnt[k], o, 64);
+    }
+    if (lane == 0) {
+      ss[wid] = s; sv[wid] = best.v; si[wid] = best.i;
+#pragma unroll
+      for (int k = 0; k < NR; ++k) sc[wid][k] = wcnt[k] + lcnt[k];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      float Ssum = ss[0];
+      ArgBest b{sv[0], si[0]};
+      for (int w = 1; w < (int)(blockDim.x >> 6); ++w) {
+        Ssum += ss[w];
+        b = better(b, ArgBest{sv[w], si[w]});
+      }
+      const float lse = __logf(Ssum);
+      nxt[r] = b.i;
+      nll_self[r] = lse - b.v;
+      if (nll_tgt != nullptr) {
+        const int t = tgt[r];
+        nll_tgt[r] = (t >= 0 && t < V) ? lse - capped1(row[t], ct, 0.f, 1) : 0.f;
+      }
+      size_t o = (size_t)r;
+      if (tk.col != nullptr) o = o * tk.W + (size_t)min(max(tk.col[r], (int64_t)0), (int64_t)(tk.W - 1));
+      o *= tk.T;
+      for (int k = 0; k < tk.T; ++k) {
+        const int id = tk.ids[(size_t)r * tk.T + k];
+        const bool ok = id >= 0 && id < V;
+        int rk = -1;
+        if (k < NR && k < tk.n_rank && ok) {
+          rk = 0;
+          for (int w = 0; w < (int)(blockDim.x >> 6); ++w) rk += sc[w][k];
+        }
+        tk.logp[o + k] = ok ? capped1(row[id], ct, 0.f, 1) - lse : 0.f;
+        tk.rank[o + k] = rk;
+      }
+    }
+    __syncthreads();   // ss / sv / si / sc are rewritten by the next row
+  }
+}
+
 // elementwise exact softcap through the compact path (ops.softcap_values; the exhaustive GPU test)
 __global__ void softcap_c_kernel(const uint16_t* __restrict__ x, float* __restrict__ y, int n, CapC cc) {
   __shared__ uint16_t lt[CAPC_MAX];
@@ -861,6 +1023,39 @@ void tb_decode_head(const uint16_t* logits, const int32_t* tgt, int32_t* nxt, fl
   else
     hipLaunchKernelGGL(decode_head_kernel<ROW_UNR>, dim3(R), dim3(512), tab_lds(reinterpret_cast<const void*>(&decode_head_kernel<ROW_UNR>), tab, attr_decode_head_kernel), st, logits, tgt, nxt,
                      nll_self, nll_tgt, V, cap, tab);
+}
+
+// decode_head + tracked-id readout (decode_head_track_kernel).  Only where tb_decode_head runs the f kernel: returns 1
+// without a registered table or for a cap outside (0, DH_FIXED_CAP], 2 under TB_DECODE_HEAD=t / c, 3 for T / n_rank
+// out of range (nothing launched); 0 on success.
+int tb_decode_head_track(const uint16_t* logits, const int32_t* tgt, int32_t* nxt, float* nll_self, float* nll_tgt,
+                         const int32_t* track, int T, int n_rank, float* logp, int32_t* rank, const int64_t* col, int W,
+                         int R, int V, float cap, hipStream_t st) {
+  if (T < 1 || T > DH_TRACK_MAX || n_rank < 0 || n_rank > T || (col != nullptr && W < 1)) return 3;
+  const uint16_t* tab = find_tab(cap, 1);
+  if (tab == nullptr || !(cap <= DH_FIXED_CAP)) return 1;
+  const char* e = getenv("TB_DECODE_HEAD");
+  if (e != nullptr && (e[0] == 't' || e[0] == 'c')) return 2;
+  if (R <= 0) return 0;
+  static const int ncu = [] {
+    int dev = 0, n = 0;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+    return n > 0 ? n : 256;
+  }();
+  const dim3 grid(std::min(R, 2 * ncu));
+  const HeadTrack tk{track, logp, rank, col, T, n_rank, W};
+  static bool attr0 = false, attr2 = false, attr4 = false, attr8 = false;
+#define TB_DH_TRACK(NR, ATTR)                                                                                         \
+  hipLaunchKernelGGL((decode_head_track_kernel<ROW_UNR, NR>), grid, dim3(512),                                        \
+                     tab_lds(reinterpret_cast<const void*>(&decode_head_track_kernel<ROW_UNR, NR>), tab, ATTR), st,    \
+                     logits, tgt, nxt, nll_self, nll_tgt, R, V, tab, tk)
+  if (n_rank == 0) TB_DH_TRACK(0, attr0);
+  else if (n_rank <= 2) TB_DH_TRACK(2, attr2);
+  else if (n_rank <= 4) TB_DH_TRACK(4, attr4);
+  else TB_DH_TRACK(8, attr8);
+#undef TB_DH_TRACK
+  return 0;
 }
 
 void tb_argmax_rows(const uint16_t* logits, int32_t* out, int R, int V, float cap, hipStream_t st) {

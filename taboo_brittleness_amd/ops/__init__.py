@@ -578,6 +578,58 @@ def decode_head(logits, cap, tgt=None, nxt=None, nll_self=None, nll_tgt=None):
     return nxt, nll_self, nll_tgt
 
 
+HEAD_TRACK_MAX = 8      # tracked columns of decode_head_track (csrc/lens.hip DH_TRACK_MAX)
+
+
+def decode_head_track(logits, cap, track, n_rank, tgt=None, nxt=None, nll_self=None, nll_tgt=None, logp=None,
+                      rank=None, col=None):
+    """:func:`decode_head` plus the output-side readout of the tracked vocab ids ``track [R, T]`` (int32,
+    ``1 <= T <= 8``, ``-1`` = empty column) in the same pass over the logits: ``logp[r, k]`` = the model's
+    next-token log-probability of ``track[r, k]`` (capped logit - the row's log-sum-exp; 0 for an empty column) and,
+    for the first ``n_rank`` columns, ``rank[r, k]`` = the number of vocab entries with a strictly greater capped
+    logit (-1 for an empty or unranked column).  ``logp`` / ``rank`` are ``[R, T]``; with ``col [R]`` (int64) they
+    are ``[R, W, T]`` buffers and row ``r`` writes column ``min(col[r], W - 1)`` only.  The GPU path is one HIP kernel
+    (csrc/lens.hip decode_head_track_kernel) and exists for the default head kernel only (``0 < cap <= 40``,
+    ``TB_DECODE_HEAD`` unset or ``f``); anything else raises.  Returns ``(nxt, nll_self, nll_tgt, logp, rank)``."""
+    V = logits.shape[-1]
+    R = logits.numel() // V
+    dev = logits.device
+    if track.dim() != 2 or track.shape[0] != R:
+        raise ValueError(f"decode_head_track: track must be [R={R}, T], got {tuple(track.shape)}")
+    T = track.shape[1]
+    if not 1 <= T <= HEAD_TRACK_MAX:
+        raise ValueError(f"decode_head_track: 1 <= T <= {HEAD_TRACK_MAX} tracked columns, got {T}")
+    if not 0 <= int(n_rank) <= T:
+        raise ValueError(f"decode_head_track: n_rank must lie in [0, {T}], got {n_rank}")
+    if logits.is_cuda and not cap > 0:
+        raise ValueError(f"decode_head_track needs a final softcap on the GPU (0 < cap <= 40), got {cap}")
+    nxt = _out(nxt, (R,), torch.int32, dev)
+    nll_self = _out(nll_self, (R,), torch.float32, dev)
+    if tgt is not None:
+        nll_tgt = _out(nll_tgt, (R,), torch.float32, dev)
+    if col is None:
+        logp = _out(logp, (R, T), torch.float32, dev)
+        rank = _out(rank, (R, T), torch.int32, dev)
+    elif logp is None or rank is None or logp.dim() != 3 or logp.shape != rank.shape or logp.shape[2] != T:
+        raise ValueError("decode_head_track: col needs logp / rank buffers of shape [R, W, T]")
+    if logits.is_cuda:
+        _softcap_table(cap, dev)
+        _k().decode_head_track(logits, tgt, nxt, nll_self, nll_tgt if tgt is not None else None, track, int(n_rank),
+                               logp, rank, col, float(cap))
+        return nxt, nll_self, nll_tgt, logp, rank
+    decode_head(logits, cap, tgt, nxt, nll_self, nll_tgt)
+    lp, rk = ref.head_track(logits, cap, track, int(n_rank))
+    if col is None:
+        logp.copy_(lp)
+        rank.copy_(rk)
+    else:
+        ar = torch.arange(R, device=dev)
+        c = col.reshape(-1).long().clamp(0, logp.shape[1] - 1)
+        logp[ar, c] = lp
+        rank[ar, c] = rk
+    return nxt, nll_self, nll_tgt, logp, rank
+
+
 def slot_copy(dst: torch.Tensor, src: torch.Tensor, dst_slots, src_slots, layers: Optional[range] = None,
               src_layers: Optional[range] = None) -> None:
     """``dst[l, dst_slots[i]] = src[l', src_slots[i]]`` for the layer ranges ``layers`` (of dst) and ``src_layers``

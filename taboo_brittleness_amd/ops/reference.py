@@ -279,6 +279,25 @@ def xent_rows(logits: torch.Tensor, tgt: torch.Tensor, cap: float, emulate_bf16:
     return torch.where(ok, lse - zt, torch.zeros_like(lse))
 
 
+def head_track(logits: torch.Tensor, cap: float, track: torch.Tensor, n_rank: int):
+    """Output-side readout of tracked vocab ids ``track [R, T]`` (``-1`` / outside ``[0, V)`` = empty) on the capped
+    values :func:`argmax_rows` / :func:`xent_rows` use: ``logp [R, T] = c(z[id]) - lse`` (0 for an empty column) and,
+    for the first ``n_rank`` columns, ``rank [R, T] = #{v : c(z[v]) > c(z[id])}`` (strict; -1 for an empty or
+    unranked column)."""
+    V = logits.shape[-1]
+    z = _capped(logits.reshape(-1, V), cap, True)
+    ids = track.reshape(z.shape[0], -1).long()
+    ok = (ids >= 0) & (ids < V)
+    zt = torch.gather(z, 1, ids.clamp(0, V - 1))
+    lse = torch.logsumexp(z, -1, keepdim=True)
+    logp = torch.where(ok, zt - lse, torch.zeros_like(zt))
+    rank = torch.full(ids.shape, -1, dtype=torch.int32, device=z.device)
+    for k in range(min(int(n_rank), ids.shape[1])):
+        cnt = (z > zt[:, k:k + 1]).sum(-1).to(torch.int32)
+        rank[:, k] = torch.where(ok[:, k], cnt, rank[:, k])
+    return logp, rank
+
+
 def gemm_nt(A: torch.Tensor, W: torch.Tensor, epi: int, bias: Optional[torch.Tensor] = None,
             thr: Optional[torch.Tensor] = None) -> torch.Tensor:
     K = A.shape[-1]

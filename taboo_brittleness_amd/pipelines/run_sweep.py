@@ -47,6 +47,8 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
                 cfg.intervention.ablation_mode != "error_preserving":
             raise ValueError(f"sae_swap / sae_swap_random are defined for ablation_mode = error_preserving only, not "
                              f"{cfg.intervention.ablation_mode!r}")
+    if cfg.intervention.output_readout and cfg.parallel.tp > 1:
+        raise ValueError("intervention.output_readout has no tensor-parallel version (parallel.tp > 1): run it with tp = 1")
     info = info or D.init_distributed(cfg.parallel.backend, cfg.runtime.device)
     tp_ctx, dp_rank, dp_size = None, info.rank, info.world
     if cfg.parallel.tp > 1:
@@ -155,6 +157,8 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
             summary["config"]["latent_score"] = runner.latent_score
         if any(m in NOISE_METHODS for m in methods):
             summary["config"]["noise_trials"] = cfg.intervention.noise_trials
+        if runner.output_readout:
+            summary["config"]["output_readout"] = True
         if swap:
             summary["config"]["swap_donor"] = runner.swap_donor
             summary["swap_skipped"] = [{"word": w, "prompt_idx": i} for w, i in runner.swap_skipped]
@@ -165,12 +169,16 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
                           "".join(json.dumps(r) + "\n" for r in allres))
         atomic_write_json(os.path.join(out_dir, "sweep_summary.json"), summary)
         lines = ["method,budget,n,p_secret_mean,p_lo,p_hi,delta_p,delta_nll,leak_rate,ll_accuracy,ll_pass10,ll_majority"]
+        ro_cols = ("delta_logp_out", "logp_out_spike_mean", "rank_out_min") if runner.output_readout else ()
+        for k in ro_cols:                            # output readout only: the other runs keep their columns
+            lines[0] += f",{k},{k}_lo,{k}_hi"
         for c in summary["curves"]:
             ll = c.get("ll_topk", {})
             lines.append(",".join(str(x) for x in [
                 c["method"], c["budget"], c["n"], c["p_secret_mean"]["mean"], c["p_secret_mean"]["lo"],
                 c["p_secret_mean"]["hi"], c["delta_p_secret"]["mean"], c["delta_nll"]["mean"], c["leak_rate"],
-                ll.get("prompt_accuracy", ""), ll.get("any_pass", ""), ll.get("global_majority_vote", "")]))
+                ll.get("prompt_accuracy", ""), ll.get("any_pass", ""), ll.get("global_majority_vote", "")] +
+                [c[k][q] for k in ro_cols for q in ("mean", "lo", "hi")]))
         atomic_write_text(os.path.join(out_dir, "sweep_curves.csv"), "\n".join(lines) + "\n")
         sw = [c for c in summary["curves"] if "p_donor_mean" in c]
         if sw:
@@ -206,7 +214,8 @@ def pair_owners(n_pairs: int, dp: int) -> List[List[int]]:
     return out
 
 
-_SHARED_FIELDS = ("resp", "p_secret", "spikes_rel", "top_ids", "nll", "gen_toks", "tok_nll", "track_probs")
+_SHARED_FIELDS = ("resp", "p_secret", "spikes_rel", "top_ids", "nll", "gen_toks", "tok_nll", "track_probs", "out_logp",
+                  "out_rank")
 
 
 def share_baselines(pairs, owned: Sequence[int], info: D.DistInfo, dev) -> None:

@@ -126,6 +126,19 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
         self.latent_score = A.check_latent_score(self.iv.latent_score)
         self.swap_donor = check_swap_donor(self.iv.swap_donor)      # donor rule of the swap methods
         self.swap_skipped: List[Tuple[str, int]] = []               # pairs the last make_cells found no donor for
+        # output-side readout (intervention.output_readout): the vocab head also reads out the next-token log-prob /
+        # rank of every pair's tracked ids (ops.decode_head_track) -- in the baseline's decode, the teacher-forced
+        # tail and the diverged cells' decode; a cell's per-position table is assembled like its lens table
+        self.output_readout = bool(getattr(self.iv, "output_readout", False))
+        if self.output_readout:
+            if getattr(model, "tp", None) is not None:
+                raise ValueError("intervention.output_readout has no tensor-parallel version: run it with tp = 1")
+            if getattr(model, "head_path", False):
+                raise ValueError("intervention.output_readout has no fused-head version: run it without --fused-head")
+            cap = float(model.spec.final_softcap or 0.0)
+            if self.dev.type == "cuda" and not 0.0 < cap <= 40.0:
+                raise ValueError(f"intervention.output_readout needs a final softcap in (0, 40] on the GPU (the tracking "
+                                 f"head kernel's range), not {cap}")
         self.exclusion = exclusion
         self.use_graphs = use_graphs
         self.prefix_share = cfg.runtime.prefix_share if prefix_share is None else prefix_share
@@ -196,11 +209,26 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
                         track.append(secret_token_id(self.tok, w2, "space"))
             for i, p in enumerate(prompts):
                 pairs.append(Pair(w, i, p, hint_prompt_ids(self.tok, p), forms, track, extra=dict(extra)))
+        if self.output_readout and pairs:
+            K = max(len(p.track) for p in pairs)
+            if K > ops.HEAD_TRACK_MAX:
+                raise ValueError(f"intervention.output_readout tracks at most {ops.HEAD_TRACK_MAX} ids per pair (two "
+                                 f"secret forms, decoys, the other words' secrets for swap runs), not {K}")
+            self._n_track = max(K, getattr(self, "_n_track", 0))
+            # ranked: the secret's two forms and, in a run with swap methods, the other words' secrets (a donor's
+            # secret is one of them); Pair.ro_order puts those columns first in the head's id table
+            self._n_rank = max(2 + max(len(p.extra) for p in pairs), getattr(self, "_n_rank", 0))
         return pairs
 
+    def _track_cols(self) -> int:
+        return getattr(self, "_n_track", 0) if self.output_readout else 0
+
     def _ensure_gen(self, S: int) -> Generator:
-        if self.gen is None or self.gen.S < S:
-            self.gen = Generator(self.m, self.B, S, use_graphs=self.use_graphs)
+        if self.gen is None or self.gen.S < S or self.gen.track_cols != self._track_cols() or \
+                (self._track_cols() and self.gen.track_rank != self._n_rank):
+            # output readout: the leading _n_rank columns of the head's id table are ranked (build_pairs)
+            tk = dict(track_cols=self._track_cols(), track_rank=self._n_rank) if self._track_cols() else {}
+            self.gen = Generator(self.m, self.B, S, use_graphs=self.use_graphs, **tk)
             self.store = torch.zeros(self.B, S + 1, self.D, dtype=self.m.dtype, device=self.dev)
             self.capture = CaptureHook(self.store)
             self._plan = None
@@ -248,6 +276,7 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
                             slots: Optional[Sequence[int]] = None) -> None:
         """``rows``: rows of ``out``/``lr``; ``slots``: their KV/capture slots (default = rows)."""
         nll = out.tok_nll.float().cpu().numpy()
+        lp_h = rk_h = None
         stop = set(int(x) for x in self.gen.stop_ids.tolist())
         slots = list(rows) if slots is None else list(slots)
         kv_dst: List[int] = []
@@ -263,6 +292,12 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
             if not p.gen_toks:   # degenerate: nothing generated at all
                 p.gen_toks = [next(iter(stop))]
             p.tok_nll = nll[i, : len(p.gen_toks)].copy()
+            if out.tok_logp is not None:
+                if lp_h is None:
+                    lp_h, rk_h = out.tok_logp.cpu().numpy(), out.tok_rank.cpu().numpy()
+                inv = np.argsort(p.ro_order())                  # head table order -> track order
+                p.out_logp = lp_h[i, : len(p.gen_toks), : len(p.track)][:, inv].copy()
+                p.out_rank = rk_h[i, : len(p.gen_toks), : len(p.track)][:, inv].copy()
             p.nll = float(p.tok_nll[:n].mean()) if n else float("nan")
             p.p_secret = lr.probs[i][:, 0].copy()
             p.track_probs = lr.probs[i].copy()
@@ -320,6 +355,8 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
             self.gen.invalidate_graph()
             self._with_basis = True
         noise, swap = self._noise_kinds(cells), self._swap_kinds(cells)
+        if self.output_readout and self.carry_rows:
+            raise ValueError("intervention.output_readout does not support the decode-tail carry-over (carry_rows > 0)")
         if any(swap) and self.carry_rows:
             raise ValueError("swap cells do not support the decode-tail carry-over (carry_rows > 0): a carried cell's "
                              "donor rows would have to move with it")
@@ -419,6 +456,13 @@ def summarize_cells(results: Sequence[dict], words: Sequence[str], word_plurals:
                     preds.setdefault(r["word"], []).append(r["guesses"])
             per_trial.append(calculate_metrics(preds, list(words), word_plurals)["overall"])
         ent["ll_topk"] = {k: float(np.mean([m[k] for m in per_trial])) for k in per_trial[0]} if per_trial else {}
+        if rs and "delta_logp_out" in rs[0]:     # output readout (intervention.output_readout) only
+            for i, key in enumerate(("delta_logp_out", "logp_out_spike_mean", "rank_out_min")):
+                ent[key] = bootstrap_ci([r[key] for r in rs if r[key] == r[key]], seed=bud + 4 + i)
+            if meth in SWAP_METHODS:
+                ent["delta_logp_out_donor"] = bootstrap_ci(
+                    [r["delta_logp_out_donor"] for r in rs if r["delta_logp_out_donor"] == r["delta_logp_out_donor"]],
+                    seed=bud + 7)
         if meth in NOISE_METHODS:                # how far the control (= its targeted twin) moved the stream
             ent["edit_norm"] = float(np.mean([r["edit_norm"] for r in rs]))
         if meth in SWAP_METHODS:                 # what the transplant did to the donor's secret

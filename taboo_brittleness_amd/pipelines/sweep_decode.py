@@ -70,6 +70,10 @@ class DecodeMixin:
         ids = [bank.names.index(p.word) if p.word in bank.names else -1 for p in slot_pairs]
         self.gen.cache.adapter[: len(ids)].copy_(torch.tensor(ids, dtype=torch.int32))
 
+    def _trk(self, row_pairs: Sequence[Pair]) -> dict:
+        """``track=`` of a prefill / decode over ``row_pairs`` (output readout only; else nothing is passed)."""
+        return {"track": [[p.track[j] for j in p.ro_order()] for p in row_pairs]} if self.output_readout else {}
+
     def _run_batch(self, pairs, batch, rb, measure_nll, bases) -> List[dict]:
         self._set_adapters([pairs[c.pair] for c in batch] + list(rb))
         if self._resumable([pairs[c.pair] for c in batch]):
@@ -100,7 +104,7 @@ class DecodeMixin:
                 pnll[b, : i + 1] = torch.from_numpy(p.tok_nll[: i + 1])
                 steps = max(steps, self.max_new - i)
             if rb:
-                first = gen.prefill([p.ids for p in rb], list(range(nc, n)), hooks)
+                first = gen.prefill([p.ids for p in rb], list(range(nc, n)), hooks, **self._trk(rb))
                 fl = first.tolist()
                 for j, p in enumerate(rb):
                     starts.append(p.plen)
@@ -109,13 +113,25 @@ class DecodeMixin:
                 steps = self.max_new
                 pnll[nc:, :1] = gen.out_nll[nc:n, :1].cpu()
             self._tick("prefix_copy+prefill")
+            ptrk = {}
+            if self.output_readout:
+                # columns <= first edit: the baseline's (their distributions come from positions before the edit)
+                K = self._n_track
+                plp = np.zeros((nc, pnll.shape[1], K), np.float32)
+                prk = np.full((nc, pnll.shape[1], K), -1, np.int32)
+                for b, p in enumerate(cell_pairs):
+                    i = c0s[b]
+                    od = p.ro_order()
+                    plp[b, :i, : len(p.track)], prk[b, :i, : len(p.track)] = p.out_logp[:i][:, od], p.out_rank[:i][:, od]
+                ptrk = dict(prefix_track=(torch.from_numpy(plp).to(self.dev), torch.from_numpy(prk).to(self.dev)))
             gen.decode(torch.tensor(toks, dtype=torch.int32), starts, prefix, steps, n, hooks, "sweep",
-                       prefix_nll=pnll.to(self.dev), teacher=[p.resp for p in cell_pairs])
+                       prefix_nll=pnll.to(self.dev), teacher=[p.resp for p in cell_pairs], **self._trk(rows_pairs),
+                       **ptrk)
             out = gen.collect(n, self.max_new, [p.plen for p in rows_pairs])
         else:
             c0s = [0] * nc
             out = gen.generate([p.ids for p in rows_pairs], self.max_new, hooks=hooks, graph_key="sweep",
-                               teacher=[p.resp for p in cell_pairs])
+                               teacher=[p.resp for p in cell_pairs], **self._trk(rows_pairs))
         self._tick("decode")
         resp = [out.response_ids(i) for i in range(n)]
         lr = self._readout(rows_pairs, out.n_gen, resp, [p.track for p in rows_pairs],
@@ -131,12 +147,14 @@ class DecodeMixin:
             nll = [float("nan")] * nc
         self._tick("nll")
         self_nll = out.tok_nll.float().cpu().numpy()
+        ro = (out.tok_logp.cpu().numpy(), out.tok_rank.cpu().numpy()) if self.output_readout and nc else None
         results = []
         for i, c in enumerate(batch):
             p = pairs[c.pair]
             results.append(self._cell_result(
                 c, p, out.n_gen[i], resp[i], lr.probs[i], lr.topk_ids[i], nll[i],
-                float(self_nll[i, : out.n_gen[i]].mean()) if out.n_gen[i] else float("nan")))
+                float(self_nll[i, : out.n_gen[i]].mean()) if out.n_gen[i] else float("nan"),
+                ro=tuple(a[i, :, : len(p.track)][:, np.argsort(p.ro_order())] for a in ro) if ro is not None else None))
         self._tick("results")
         return results
 
@@ -235,7 +253,8 @@ class DecodeMixin:
         # carried over from the previous batch (carry-region slots), longest remaining decode first
         R_start, R_tok, R_slot, R_steps, R_ps, R_lo, R_hi, R_pref, R_nll = [], [], [], [], [], [], [], [], []
         if nr:
-            first = gen.prefill([p.ids for p in rb], list(range(nc, nc + nr)), hooks, out_rows=list(range(nr)))
+            first = gen.prefill([p.ids for p in rb], list(range(nc, nc + nr)), hooks, out_rows=list(range(nr)),
+                                **self._trk(rb))
             fl = np.asarray(first.tolist(), np.int64)
             z = np.zeros(nr, np.int64)
             R_start.append(np.asarray([p.plen for p in rb], np.int64))
@@ -337,7 +356,8 @@ class DecodeMixin:
                              prefix_rows=(pre_slot, pre_lo, pre_hi),
                              stop_below=self.carry_rows if carry_ok else 0,
                              min_steps=max([cr.steps for cr in carry_in] + [0]),
-                             share_keys=skeys, share_split=self.layer if skeys is not None else None)
+                             share_keys=skeys, share_split=self.layer if skeys is not None else None,
+                             **(self._trk(rb + [cell_pairs[src[1]] for src in row_src]) if self.output_readout else {}))
             if skeys is not None:
                 self.stats["decode_lo_rows_run"] += gen.last_rows_lo
                 self.stats["decode_lo_groups"] += gen.last_groups
@@ -386,7 +406,7 @@ class DecodeMixin:
         # a staged next tail overwrites the cell slots (_launch_staged_next runs it at that point)
         self._carry_move_pending = carry_move
         if entries:
-            results = self._resume_readout(entries, out)
+            results = self._resume_readout(entries, out, tf)
         else:
             # nothing to read out (every cell carried on): still launch the announced next batch now, so a
             # stale announcement is never staged during a later readout

@@ -29,14 +29,15 @@ TAIL_CHUNK_ROWS = 32768
 class ReadoutMixin:
     """Methods of :class:`~.sweep.SweepRunner` (state lives on the runner; see its docstring)."""
 
-    def _resume_readout(self, entries, out) -> List[dict]:
+    def _resume_readout(self, entries, out, tf: Optional[dict] = None) -> List[dict]:
         """Lens readout + result records of layer-resumed cells.  The host side is columnar: one set of
         numpy arrays for the whole batch (no per-cell Python work on the launching thread); every
         non-diverged cell of a pair shares the pair's response, spikes and exclusions.
 
         ``entries``: per cell ``(cell, pair, slot, D or None, nll_edit, self_nll or None, out row or None, f)``
         — ``slot`` holds its capture-store rows, diverged cells read their response from ``out``; spikes before
-        the cell's effective first edit ``f`` were no-op edits, their lens is the baseline's."""
+        the cell's effective first edit ``f`` were no-op edits, their lens is the baseline's.  ``tf`` (output
+        readout only): the batch's finished teacher-forced tail, whose tracked rows fill the cells' tables."""
         m = self.m
         S1 = self.store.shape[1]
         E_n = len(entries)
@@ -153,6 +154,13 @@ class ReadoutMixin:
                 "cell_of": cell_of, "host_tok": host_tok,
                 # swap cells: their donor pairs, resolved now (the records may be built after the next call began)
                 "donors": [self._run_pairs[c.donor] if c.donor >= 0 else None for c in batch]}
+        if self.output_readout:
+            # the pieces of every cell's output-readout table: the tail's rows (row r0 + t - f = index t + 1) and, for
+            # diverged cells, the decode's columns (host copies now: the buffers are reused by the next batch)
+            cols["ro"] = {"lp": tf.get("logp"), "rk": tf.get("rank"), "r0": tf["r0"][slot_a], "E": tf["E"][slot_a],
+                          "f": f_e,
+                          "dlp": out.tok_logp.cpu().numpy() if div.any() else None,
+                          "drk": out.tok_rank.cpu().numpy() if div.any() else None}
         if getattr(self, "_defer", False):
             return self._records_pool().submit(self._resume_records, batch, cell_pairs, cols, pr, vh, ih, K)
         return self._resume_records(batch, cell_pairs, cols, pr, vh, ih, K)
@@ -233,17 +241,72 @@ class ReadoutMixin:
         ps_max = np.where(valid, P3[:, :, 0], -np.inf).max(1) if nc else np.zeros(0)
         decoy = (np.where(valid[:, :, None], P3[:, :, 2:], 0.0).sum(1) / cnt[:, None]) if K > 2 else None
         results = []
+        ro = cols.get("ro")
         for b, (c, p) in enumerate(zip(batch, cell_pairs)):
             ng = int(ng_a[b])
             resp = host_tok[j_a[b], :ng].tolist() if div[b] else p.resp
+            rot = None
+            if ro is not None:
+                rot = self._out_table(p, ng, int(ro["f"][b]), int(ro["E"][b]), int(ro["r0"][b]),
+                                      int(d_a[b]) if div[b] else None, ro["lp"], ro["rk"],
+                                      (ro["dlp"][j_a[b]], ro["drk"][j_a[b]]) if div[b] else None)
             topk = ih[b].tolist() if ng > 0 and vh[b] > 0 else []
             stats = (float(ps_mean[b]), float(ps_final[b]), float(ps_max[b])) if ng else (0.0, 0.0, 0.0)
             dec = decoy[b, : p.n_decoys].tolist() if (decoy is not None and ng and p.n_decoys > 0) else []
             q = cols["donors"][b]
             results.append(self._cell_record(c, p, ng, resp, stats, dec, topk, float(cols["nll"][b]),
                                              float(cols["sn"][b]), q,
-                                             P3[b, :ng, p.extra.get(q.word, 0)] if q is not None else None))
+                                             P3[b, :ng, p.extra.get(q.word, 0)] if q is not None else None, ro=rot))
         return results
+
+    @staticmethod
+    def _out_table(p: Pair, ng: int, f: int, E: int, r0: int, D: Optional[int], lp, rk, dec):
+        """A layer-resumed cell's output-readout table ``(logp, rank) [ng, K]``, assembled like its lens table ``P3``:
+        the baseline's rows for indices ``<= f`` (the distribution choosing token ``i`` comes from position ``i - 1``,
+        before the first edit), tail row ``t`` at index ``t + 1`` up to the divergence ``D`` (undiverged: to the
+        tail's end), the decode's own columns from ``D + 1`` on."""
+        K = len(p.track)
+        inv = np.argsort(p.ro_order())                # the head's table order -> track order (the baseline's is)
+        LP = np.zeros((ng, K), np.float32)
+        RK = np.full((ng, K), -1, np.int32)
+        nb = min(f + 1, ng, p.out_logp.shape[0])
+        LP[:nb], RK[:nb] = p.out_logp[:nb, :K], p.out_rank[:nb, :K]
+        hi = min((E if D is None else min(E, D - 1)) + 2, ng)          # tail indices f + 1 .. hi - 1
+        if hi > f + 1 and lp is not None:
+            LP[f + 1: hi] = lp[r0: r0 + hi - f - 1, :K][:, inv]
+            RK[f + 1: hi] = rk[r0: r0 + hi - f - 1, :K][:, inv]
+        if D is not None and dec is not None and ng > D + 1:
+            LP[D + 1: ng] = dec[0][D + 1: ng, :K][:, inv]
+            RK[D + 1: ng] = dec[1][D + 1: ng, :K][:, inv]
+        return LP, RK
+
+    @staticmethod
+    def _out_fields(p: Pair, lp: np.ndarray, rk: np.ndarray, donor: Optional[Pair] = None) -> dict:
+        """Record fields of the output readout from a per-position table ``(logp, rank) [n, K]`` (one code path for
+        every way the table was obtained, so equal tables give equal fields).  Per position ``s_i`` = max log-prob and
+        ``r_i`` = min rank over the secret's two forms.  ``logp_out_spike_mean`` runs over the pair's spikes: every
+        cell edits all of its pair's spikes (its plan row takes ``Pair.spikes_abs[:spikes_k]``, and ``select_spikes``
+        returns at most ``spikes_k``), so these are the cell's edited spikes."""
+        n = lp.shape[0]
+        nan = float("nan")
+        out = {"logp_out_mean": nan, "logp_out_max": nan, "logp_out_final": nan, "logp_out_spike_mean": nan,
+               "rank_out_min": -1, "rank_out_median": nan, "decoy_logp_out": []}
+        ok = [k for k in (0, 1) if k < len(p.track) and p.track[k] >= 0]
+        if n and ok:
+            s = lp[:, ok].astype(np.float64).max(1)
+            r = rk[:, ok].astype(np.int64)
+            r = np.where(r < 0, np.iinfo(np.int64).max, r).min(1)
+            sp = [t + 1 for t in p.spikes_rel if t + 1 < n]
+            out.update({"logp_out_mean": float(s.mean()), "logp_out_max": float(s.max()), "logp_out_final": float(s[-1]),
+                        "logp_out_spike_mean": float(s[sp].mean()) if sp else nan,
+                        "rank_out_min": int(r.min()), "rank_out_median": float(np.median(r))})
+        if n and p.n_decoys > 0:
+            out["decoy_logp_out"] = lp[:, 2: 2 + p.n_decoys].astype(np.float64).mean(0).tolist()
+        if donor is not None:
+            col = p.extra.get(donor.word, 0)
+            out["logp_out_donor_mean"] = float(lp[:, col].astype(np.float64).mean()) if n else nan
+            out["rank_out_donor_min"] = int(rk[:, col].min()) if n else -1
+        return out
 
     @torch.no_grad()
     def _ensure_cum(self, pairs: Sequence[Pair]) -> None:
@@ -359,12 +422,17 @@ class ReadoutMixin:
         """Host side of a launched teacher-forced tail: wait for its one D2H copy, split it."""
         pend = res.pop("_pending", None)
         if pend is not None:
-            host, ev, M = pend
+            flat, ev, M = pend
             if ev is not None:
                 ev.synchronize()
+            host = flat[: 3 * M].view(3, M)
             res["nxt"] = host[0, :M].view(torch.int32).numpy()
             res["nll_self"] = host[1, :M].numpy()
             res["nll_tgt"] = host[2, :M].numpy()
+            if flat.numel() > 3 * M:         # output readout: [M, K] log-probs, then [M, K] ranks (int32 bits)
+                K = (flat.numel() - 3 * M) // (2 * M)
+                res["logp"] = flat[3 * M: 3 * M + M * K].view(M, K).numpy()
+                res["rank"] = flat[3 * M + M * K:].view(torch.int32).view(M, K).numpy()
         return res
 
     @torch.no_grad()
@@ -424,8 +492,21 @@ class ReadoutMixin:
         pos_d = up_(pos)
         slot_d = up_(slot)
         tgt_d = up_(tgt)
-        outs = torch.empty(3, M, dtype=torch.float32, device=dev)      # [greedy id bits, NLL self, NLL target]
+        # [greedy id bits, NLL self, NLL target], then with the output readout the rows' tracked log-probs and ranks:
+        # one buffer, one D2H copy
+        Kt = self._track_cols()
+        flat = torch.empty(3 * M + 2 * M * Kt, dtype=torch.float32, device=dev)
+        outs = flat[: 3 * M].view(3, M)
         nxt, ns, nt = outs[0].view(torch.int32), outs[1], outs[2]
+        ro = None
+        if Kt:
+            # tail row t's logits are the distribution that chooses response token t + 1.  The [U, K] id table goes
+            # up once per launch; every row picks its pair's ids by its pair-table index
+            ttab = np.full((max(1, len(ulist)), Kt), -1, np.int32)
+            for u, (p, _) in enumerate(ulist):
+                ttab[u, : len(p.track)] = np.asarray(p.track)[p.ro_order()]
+            ro = (up_(ttab).index_select(0, up_(up_a[rb_])), flat[3 * M: 3 * M + M * Kt].view(M, Kt),
+                  flat[3 * M + M * Kt:].view(torch.int32).view(M, Kt))
         rpb = 16 // max(1, m.lspec.heads // m.lspec.kv_heads)
         cap = TAIL_CHUNK_ROWS
         # vocab-head rows per GEMM: 256-row multiples (GEMM tiles) of at most HEAD_LOGITS_BYTES of bf16 logits
@@ -472,26 +553,27 @@ class ReadoutMixin:
                 hk.use_table(acts_tab, tb_d)
         try:
             self._tf_chunks(chunks, streams, tab_d, tab_off, pos_d, slot_d, tgt_d, src_d, H, ws_rows, step, hooks,
-                            nxt, ns, nt)
+                            nxt, ns, nt, ro)
         finally:
             for hk in splice:
                 hk.use_table(None)
         if len(streams) > 1:
             main.wait_stream(streams[1])
         if dev.type == "cuda":
-            host = torch.empty(3, M, dtype=torch.float32, pin_memory=True)
-            host.copy_(outs, non_blocking=True)
+            host = torch.empty(flat.shape, dtype=torch.float32, pin_memory=True)
+            host.copy_(flat, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(dev))
         else:
-            host, ev = outs, None
+            host, ev = flat, None
         res["_pending"] = (host, ev, M)
         self._tick("tf_launched")
         return res
 
     def _tf_chunks(self, chunks, streams, tab_d, tab_off, pos_d, slot_d, tgt_d, src_d, H, ws_rows, step, hooks,
-                   nxt, ns, nt) -> None:
-        """The packed forwards + vocab heads of :meth:`_tf_launch`, chunk by chunk."""
+                   nxt, ns, nt, ro=None) -> None:
+        """The packed forwards + vocab heads of :meth:`_tf_launch`, chunk by chunk.  ``ro`` (output readout): the rows'
+        tracked ids ``[M, K]`` and the ``[M, K]`` log-prob / rank outputs of the tracking head."""
         m, dev = self.m, self.dev
         for ci, (c0, c1, chunk) in enumerate(chunks):
             st = streams[ci % len(streams)]
@@ -520,23 +602,28 @@ class ReadoutMixin:
                     # the unembedding runs on whole 256-row tiles (padding rows of x included) so the
                     # GEMM shapes stay few and tuned; only the real rows are read out
                     lg = m.logits(x[q0:min(Mp, q0 + step)])[: q1 - q0]
+                    if ro is not None:
+                        ops.decode_head_track(lg, m.spec.final_softcap, ro[0][c0 + q0:c0 + q1], self._n_rank,
+                                              tgt_d[c0 + q0:c0 + q1], nxt[c0 + q0:c0 + q1], ns[c0 + q0:c0 + q1],
+                                              nt[c0 + q0:c0 + q1], ro[1][c0 + q0:c0 + q1], ro[2][c0 + q0:c0 + q1])
+                        continue
                     ops.decode_head(lg, m.spec.final_softcap, tgt_d[c0 + q0:c0 + q1], nxt[c0 + q0:c0 + q1],
                                     ns[c0 + q0:c0 + q1], nt[c0 + q0:c0 + q1])
 
     def _cell_result(self, c: Cell, p: Pair, n_gen: int, resp: List[int], probs: np.ndarray, topk_ids: List[int],
-                     nll_edit: float, nll_self: float) -> dict:
+                     nll_edit: float, nll_self: float, ro=None) -> dict:
         ps = probs[:, 0] if probs.shape[0] else np.zeros(0, dtype=np.float32)
         stats = (float(ps.mean()), float(ps[-1]), float(ps.max())) if ps.size else (0.0, 0.0, 0.0)
         dec = [float(x) for x in probs[:, 2: 2 + p.n_decoys].mean(0)] if probs.shape[0] else []
         q = self._run_pairs[c.donor] if c.donor >= 0 else None
         return self._cell_record(c, p, n_gen, resp, stats, dec, topk_ids, nll_edit, nll_self, q,
-                                 probs[:, p.extra.get(q.word, 0)] if q is not None else None)
+                                 probs[:, p.extra.get(q.word, 0)] if q is not None else None, ro=ro)
 
     def _cell_record(self, c: Cell, p: Pair, n_gen: int, resp: List[int], stats: Tuple[float, float, float],
                      decoy: List[float], topk_ids: List[int], nll_edit: float, nll_self: float,
-                     donor: Optional[Pair] = None, p_donor: Optional[np.ndarray] = None) -> dict:
+                     donor: Optional[Pair] = None, p_donor: Optional[np.ndarray] = None, ro=None) -> dict:
         """``donor`` / ``p_donor`` (swap cells only): the donor pair and the lens probability of its secret (space
-        form) over the cell's response."""
+        form) over the cell's response.  ``ro`` (output readout only): the cell's ``(logp, rank) [n_gen, K]`` table."""
         dc = self._dec_cache
         guesses = []
         for t in topk_ids:
@@ -581,6 +668,15 @@ class ReadoutMixin:
                 "donor_leak": contains_secret(self.tok.decode(resp), q.forms),
                 "donor_in_topk": int(q.track[0]) in [int(t) for t in topk_ids],
             })
+        if ro is not None:                       # output readout only: the other runs keep their keys
+            n = len(p.resp)
+            base = self._out_fields(p, p.out_logp[:n], p.out_rank[:n], donor if c.method in SWAP_METHODS else None)
+            f = self._out_fields(p, ro[0][:n_gen], ro[1][:n_gen], donor if c.method in SWAP_METHODS else None)
+            f["delta_logp_out"] = f["logp_out_mean"] - base["logp_out_mean"]
+            f["logp_out_mean_base"] = base["logp_out_mean"]
+            if "logp_out_donor_mean" in f:
+                f["delta_logp_out_donor"] = f["logp_out_donor_mean"] - base["logp_out_donor_mean"]
+            rec.update(f)
         return rec
 
     def _nll_ws(self, M: int, key: int = 0):

@@ -78,6 +78,18 @@ class Pair:
     # swap methods only: word -> column of ``track`` holding that other word's secret id (space form), appended after
     # the decoys (SweepRunner.build_pairs); the decoy readouts stop before these columns
     extra: Dict[str, int] = field(default_factory=dict)
+    # intervention.output_readout only: [len(gen_toks), K] next-token log-prob / rank of ``track`` under the
+    # distribution that chose each generated token (index 0: the prefill's last prompt row), from the baseline's decode
+    out_logp: Optional[np.ndarray] = None
+    out_rank: Optional[np.ndarray] = None
+
+    def ro_order(self) -> List[int]:
+        """Column order of ``track`` in the tracking head's id table (output readout): the secret's two forms, the
+        other words' secrets, then the decoys -- the head ranks a leading block of columns, and a swap donor's secret
+        must be inside it while the decoys need not.  Table column ``j`` holds ``track[ro_order()[j]]``;
+        ``np.argsort`` of it maps a table back to ``track`` order (``table[..., inv]``)."""
+        ex = sorted(self.extra.values())
+        return list(range(min(2, len(self.track)))) + ex + [j for j in range(2, len(self.track)) if j not in ex]
 
     @property
     def n_decoys(self) -> int:

@@ -86,21 +86,42 @@ def _hooks_for(B: int, layer: int, sae, edit: Optional[Dict], device,
     return {layer: [EditHook(plan, sae if kind in SAE_KINDS else None)]}
 
 
+def secret_track(tok, word: str) -> List[int]:
+    """The tracked ids of a forcing row under ``intervention.output_readout``: the secret's space and bare forms."""
+    from ..models.tokenizer import secret_token_id
+
+    return [secret_token_id(tok, word, "space"), secret_token_id(tok, word, "bare")]
+
+
+def first_readout(o, i: int):
+    """``(logp_secret_first, rank_secret_first)`` of output row ``i``: the readout of the first answer token's
+    distribution (column 0, from the prefill's last row -- right after the prefilled phrase): the larger log-prob
+    and the smaller rank of the secret's two forms."""
+    lp, rk = o.tok_logp[i, 0].tolist(), [r for r in o.tok_rank[i, 0].tolist() if r >= 0]
+    return float(max(lp)), int(min(rk)) if rk else -1
+
+
 def _generate(model, rows: List[List[int]], max_new: int, hooks, batch: Optional[int] = None,
-              groups: Optional[Sequence[int]] = None) -> List[List[int]]:
+              groups: Optional[Sequence[int]] = None, track: Optional[Sequence[Sequence[int]]] = None,
+              first: Optional[list] = None) -> List[List[int]]:
     """Greedy completions of ``rows``; ``groups``: rows of one group share a prompt prefix (the chat history
-    before the prefilled phrase), prefilled once per group (``Generator.generate_shared``)."""
+    before the prefilled phrase), prefilled once per group (``Generator.generate_shared``).  ``track`` (output
+    readout): per row its tracked ids; ``first`` then receives every row's :func:`first_readout`."""
     out: List[List[int]] = []
     B = batch or len(rows)
     S = max(len(r) for r in rows) + max_new + 1
-    gen = Generator(model, B, S, use_graphs=GRAPHS)
+    tk = dict(track_cols=2, track_rank=2) if track is not None else {}
+    gen = Generator(model, B, S, use_graphs=GRAPHS, **tk)
     for c0 in range(0, len(rows), B):
         chunk = rows[c0:c0 + B]
+        tkw = dict(track=list(track[c0:c0 + B])) if track is not None else {}
         if groups is not None and SHARE_PREFIX:
-            o = gen.generate_shared(chunk, list(groups[c0:c0 + B]), max_new, hooks=hooks, graph_key="forcing")
+            o = gen.generate_shared(chunk, list(groups[c0:c0 + B]), max_new, hooks=hooks, graph_key="forcing", **tkw)
         else:
-            o = gen.generate(chunk, max_new, hooks=hooks, graph_key="forcing")
+            o = gen.generate(chunk, max_new, hooks=hooks, graph_key="forcing", **tkw)
         out += [o.response_ids(i) for i in range(len(chunk))]
+        if track is not None and first is not None:
+            first += [first_readout(o, i) for i in range(len(chunk))]
     return out
 
 
@@ -159,14 +180,20 @@ def run_forcing(cfg: Config, model, tok, words: Sequence[str], mode: str = "post
             ids = conversation_ids(tok, [{"role": "user", "content": ph}], add_generation_prompt=True)
         rows.append(ids)
     comps_mine = []
+    readout = bool(cfg.intervention.output_readout)       # + the continuous score behind the success verdict
+    firsts: list = []
     if rows:
         hooks = _hooks_for(len(rows), layer, sae, edit, dev, amode, cval)
         comps_mine = _generate(model, rows, tf.max_new_tokens if mode != "naive" else cfg.experiment.max_new_tokens,
-                               hooks, groups=[words.index(all_keys[i][0]) for i in mine])
+                               hooks, groups=[words.index(all_keys[i][0]) for i in mine],
+                               track=[secret_track(tok, all_keys[i][0]) for i in mine] if readout else None,
+                               first=firsts)
+    if readout:
+        comps_mine = [(c, f) for c, f in zip(comps_mine, firsts)]
     got = dp.gather({i: c for i, c in zip(mine, comps_mine)})
     preds: Dict[str, List[List[str]]] = {w: [] for w in words}
     for i, (w, ph) in enumerate(all_keys):
-        c = got[i]
+        c, fr = got[i] if readout else (got[i], None)
         text = tok.decode(c)
         forms = cfg.word_plurals.get(w, [w])
         ok = contains_secret(text, forms)
@@ -174,6 +201,8 @@ def run_forcing(cfg: Config, model, tok, words: Sequence[str], mode: str = "post
         # a success counts as a correct guess even if the secret is not the first word
         preds[w].append([forms[0]] if ok else ([g] if g else []))
         records.append({"word": w, "phrase": ph, "completion": text, "success": ok, "guess": g})
+        if readout:                                      # output readout only: the other runs keep their keys
+            records[-1]["logp_secret_first"], records[-1]["rank_secret_first"] = fr
     metrics = calculate_metrics(preds, list(words), cfg.word_plurals)
     for w in words:
         metrics[w]["predictions"] = preds[w]
@@ -272,7 +301,7 @@ def settings_alpha(settings: Sequence[Dict]) -> float:
 
 
 def _forcing_state(model, rows: int, S: int, settings: Sequence[Dict], layer: int, sae,
-                   mode: str = "error_preserving") -> Dict:
+                   mode: str = "error_preserving", track_cols: int = 0) -> Dict:
     mmax = max([len(st["latents"]) for st in settings if st.get("kind") in SAE_KINDS] + [1])
     nb = sum(int(st["basis"].shape[0]) for st in settings if st.get("kind") in PROJ_KINDS)
     alpha = settings_alpha(settings)
@@ -280,10 +309,12 @@ def _forcing_state(model, rows: int, S: int, settings: Sequence[Dict], layer: in
     noise = tuple(any(st.get("kind") == k for st in settings) for k in ("sae_noise", "proj_noise"))
     key = id(model)
     ent = _FORCING_STATE.get(key)
-    if ent is None or ent["rows"] < rows or ent["S"] < S:
+    if ent is None or ent["rows"] < rows or ent["S"] < S or ent["gen"].track_cols != track_cols:
         _FORCING_STATE.clear()                     # one KV cache alive at a time
         S_alloc = -(-max(S, ent["S"] if ent else 0) * 5 // 4 // 64) * 64   # headroom for the longer later turns
-        ent = {"rows": rows, "S": S_alloc, "gen": Generator(model, rows, S_alloc, use_graphs=GRAPHS), "hooks": None}
+        tk = dict(track_cols=track_cols, track_rank=track_cols) if track_cols else {}
+        ent = {"rows": rows, "S": S_alloc, "gen": Generator(model, rows, S_alloc, use_graphs=GRAPHS, **tk),
+               "hooks": None}
         _FORCING_STATE[key] = ent
     h = ent["hooks"]
     sig = (ent["rows"], mmax, nb, model.spec.hidden, layer, id(need_sae), mode, noise, alpha)
@@ -352,6 +383,10 @@ def run_forcing_settings(cfg: Config, model, tok, settings: Sequence[Dict], mode
         # turns of one call may resume (another call's settings of the same count and kinds edit differently)
         ent_.pop("prev", None)
 
+    readout = bool(cfg.intervention.output_readout)       # the answers' first-token readout of the secret
+    strack = [secret_track(tok, st["word"]) for st in settings] if readout else None
+    firsts: list = []
+
     def generate(rows: List[List[int]], row_setting: List[int], max_new: int, share: bool = False) -> List[List[int]]:
         # one Generator (KV cache + decode graphs) and one fixed-shape edit plan serve every chunk, turn and call
         out: List[List[int]] = []
@@ -362,7 +397,7 @@ def run_forcing_settings(cfg: Config, model, tok, settings: Sequence[Dict], mode
             reuse = ent0 is not None and ent0["S"] >= S and ent0["rows"] >= min(len(rows), FORCING_MAX_ROWS)
             chunk = min(len(rows), ent0["rows"]) if reuse else _auto_rows(model, len(rows), S)
         R = min(chunk, max(len(rows), 1))
-        ent = _forcing_state(model, R, S, settings, layer, sae, amode)
+        ent = _forcing_state(model, R, S, settings, layer, sae, amode, track_cols=2 if readout else 0)
         gen, fh = ent["gen"], ent["hooks"]
         # the previous single-chunk call's prompts, still in the cache slots under the same edits (the warm-up turn
         # before this one): each row's new prompt re-prefills only what follows its longest common token prefix
@@ -373,23 +408,27 @@ def run_forcing_settings(cfg: Config, model, tok, settings: Sequence[Dict], mode
             chunk, cs = rows[c0:c0 + R], row_setting[c0:c0 + R]
             edited = fh.fill(settings, cs, cfg.intervention.clamp_value)
             hooks, gk = (fh.hooks, "forcing") if edited else (None, "forcing_plain")
+            tkw = dict(track=[strack[si] for si in cs]) if readout else {}
             if share and SHARE_PREFIX:                   # a setting's answers share its chat history
-                o = gen.generate_shared(chunk, cs, max_new, hooks=hooks, graph_key=gk)
+                o = gen.generate_shared(chunk, cs, max_new, hooks=hooks, graph_key=gk, **tkw)
             else:
                 keep = None
                 if (RESUME_TURNS and single and prev is not None and prev["fh"] is fh and prev["gen"] is gen
                         and prev["cs"] == list(cs) and prev["edited"] == edited):
                     keep = [_lcp(a_, b_) for a_, b_ in zip(chunk, prev["rows"])]
-                o = gen.generate(chunk, max_new, hooks=hooks, graph_key=gk, keep=keep)
+                o = gen.generate(chunk, max_new, hooks=hooks, graph_key=gk, keep=keep, **tkw)
                 if single:
                     ent["prev"] = {"rows": [list(r) for r in chunk], "cs": list(cs), "fh": fh, "gen": gen,
                                    "edited": edited}
                 for k_, v_ in getattr(gen, "last_phases", {}).items():
                     clk["gen_" + k_] = clk.get("gen_" + k_, 0.0) + v_
             out += [o.response_ids(i) for i in range(len(chunk))]
+            if readout and answers[0]:
+                firsts.extend(first_readout(o, i) for i in range(len(chunk)))
         return out
 
     import time as _time
+    answers = [False]                                     # the call that generates the answers (not a warm-up turn)
 
     clk = {"host": 0.0, "warmup_gen": 0.0, "answer_gen": 0.0}
     t_ = _time.perf_counter()
@@ -421,6 +460,7 @@ def run_forcing_settings(cfg: Config, model, tok, settings: Sequence[Dict], mode
             owner.append(si)
     t1 = _time.perf_counter()
     clk["host"] += t1 - t_
+    answers[0] = True
     comps = generate(rows, owner, tf.max_new_tokens if mode != "naive" else cfg.experiment.max_new_tokens,
                      share=(mode == "postgame"))
     t_ = _time.perf_counter()
@@ -433,6 +473,11 @@ def run_forcing_settings(cfg: Config, model, tok, settings: Sequence[Dict], mode
         ok = contains_secret(tok.decode(c), cfg.word_plurals.get(w, [w]))
         res[si]["successes"] += int(ok)
         res[si]["n"] += 1
+    if readout:      # per setting: the mean log-prob and the median rank of the secret over its phrases' first tokens
+        for si, r in enumerate(res):
+            fr = [f for s_, f in zip(owner, firsts) if s_ == si]
+            r["logp_secret_first"] = float(np.mean([f[0] for f in fr])) if fr else float("nan")
+            r["rank_secret_first"] = float(np.median([f[1] for f in fr])) if fr else float("nan")
     for r in res:
         r["success_rate"] = r["successes"] / max(1, r["n"])
         r["ablation_mode"] = amode

@@ -183,6 +183,33 @@ def content_vs_inhibition(summary: Dict, path: str, forcing_delta: Optional[Dict
     plt.close(fig)
 
 
+def content_vs_output(summary: Dict, path: str) -> None:
+    """Output-side readout (intervention.output_readout): what an edit does to the lens content at the hooked layer
+    (Δ LL secret probability) against what it does to the model's own next-token log-prob of the secret
+    (``delta_logp_out``), one point per (method, budget) with the 95 % bootstrap interval of the latter."""
+    fig, ax = plt.subplots(figsize=(6, 5))
+    for c in summary["curves"]:
+        if "delta_logp_out" not in c:
+            continue
+        x, y = c["delta_p_secret"]["mean"], c["delta_logp_out"]
+        col = "tab:red" if c["method"].endswith("targeted") else \
+            "tab:green" if c["method"].endswith("noise") else "tab:purple" if "swap" in c["method"] else "tab:blue"
+        mk = "o" if c["method"].startswith("sae") else "s"
+        ax.errorbar([x], [y["mean"]], yerr=[[y["mean"] - y["lo"]], [y["hi"] - y["mean"]]], color=col, marker=mk,
+                    capsize=2, lw=0.8)
+        ax.annotate(f"{c['method'].split('_')[0]}{c['budget']}", (x, y["mean"]), fontsize=7)
+    ax.axvline(0, color="k", lw=0.5)
+    ax.axhline(0, color="k", lw=0.5)
+    ax.set_xlabel("Δ LL secret probability at the hooked layer (content)")
+    ax.set_ylabel("Δ next-token log-prob of the secret (output)")
+    if mode_label(summary):
+        ax.set_title(f"sae cells: {mode_label(summary)}")
+    plt.tight_layout()
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    fig.savefig(path, dpi=150)
+    plt.close(fig)
+
+
 def baselines_table(rows: Dict[str, Dict[str, float]], path: str) -> None:
     lines = ["method,pass@10,majority@10,accuracy"]
     for name, m in rows.items():
@@ -216,6 +243,10 @@ def make_report(results_dir: str, out_dir: str) -> List[str]:
                   if s.get("forcing") else None)
             content_vs_inhibition(s, p, fd)
             made.append(p)
+            if any("delta_logp_out" in c for c in s["curves"]):    # only sweeps run with the output readout
+                p = os.path.join(out_dir, f"fig3b_content_vs_output_{tag}.png")
+                content_vs_output(s, p)
+                made.append(p)
             if s.get("baselines"):
                 from .dashboards import write_latent_dashboard
 

@@ -54,6 +54,10 @@ class GenerationOutput:
     stopped: List[bool]
     tok_nll: Optional[torch.Tensor] = None   # [n, max_new] NLL of each generated token under the (edited) model
     tf_nll: Optional[torch.Tensor] = None    # [n, max_new] NLL of the teacher's token at each column
+    # output-side readout (Generator(track_cols=T)): [n, max_new, T] log-prob / rank of the row's tracked vocab ids
+    # under the distribution that chose each column (rank: -1 for empty / unranked columns); None when off
+    tok_logp: Optional[torch.Tensor] = None
+    tok_rank: Optional[torch.Tensor] = None
 
     def host_tokens(self) -> np.ndarray:
         host = self.__dict__.get("_host")
@@ -69,7 +73,12 @@ class Generator:
     """Greedy batched generator bound to one model and one batch geometry."""
 
     def __init__(self, model: Gemma2Model, batch: int, max_len: int, use_graphs: bool = True,
-                 stop_ids: Sequence[int] = (1, 107), pad_id: int = 0, final_softcap: Optional[float] = None):
+                 stop_ids: Sequence[int] = (1, 107), pad_id: int = 0, final_softcap: Optional[float] = None,
+                 track_cols: int = 0, track_rank: int = 2):
+        """``track_cols = T > 0``: every head pass also reads out the log-prob of ``T`` tracked vocab ids per row and
+        the rank of the first ``min(track_rank, T)`` of them (``ops.decode_head_track``; ids set per call by
+        ``decode(track=)`` / ``prefill(track=)``) into ``out_logp`` / ``out_rank [B, W, T]``.  0: nothing is
+        allocated and every step is what it is without the feature."""
         self.m = model
         self.B = batch
         self.S = max_len
@@ -98,6 +107,18 @@ class Generator:
         self.tf_nll_step = torch.empty(B, dtype=torch.float32, device=self.dev)
         self.tgt_logit = torch.empty(B, dtype=torch.float32, device=self.dev)     # fused head scratch
         self.out_tf_nll = torch.zeros(B, self.W, dtype=torch.float32, device=self.dev)
+        self.track_cols = int(track_cols)
+        self.track_rank = min(int(track_rank), self.track_cols)
+        self.track = self.out_logp = self.out_rank = None
+        if self.track_cols:
+            if not 1 <= self.track_cols <= ops.HEAD_TRACK_MAX:
+                raise ValueError(f"track_cols must lie in [0, {ops.HEAD_TRACK_MAX}], got {track_cols}")
+            if getattr(model, "head_path", False):
+                raise ValueError("output readout (track_cols) has no fused-head / vocab-parallel-head version: "
+                                 "run with the logits GEMM + decode_head (no --fused-head, no vocab-parallel TP)")
+            self.track = torch.full((B, self.track_cols), -1, dtype=torch.int32, device=self.dev)
+            self.out_logp = torch.zeros(B, self.W, self.track_cols, dtype=torch.float32, device=self.dev)
+            self.out_rank = torch.full((B, self.W, self.track_cols), -1, dtype=torch.int32, device=self.dev)
         self._graphs: Dict[tuple, "torch.cuda.CUDAGraph"] = {}
         self.ws = model.workspace(batch)       # pinned: captured graphs hold these pointers (and row views)
         self.kv_prefix: Optional[KVPrefix] = None
@@ -220,6 +241,13 @@ class Generator:
             # fused GEMM head; its partial workspace lives in the (then idle) logits buffer
             self.m.head(x, self.cap, self.tf_step[:nb], self.nxt[:nb], self.nll_step[:nb], self.tf_nll_step[:nb],
                         part=self.logits.view(torch.float32), tgt_logit=self.tgt_logit[:nb])
+        elif self.track_cols:
+            # tracked readout straight into column step_idx of out_logp / out_rank (before decode_post advances it)
+            lg = self.logits[:nb]
+            self.m.logits(x, out=lg)
+            ops.decode_head_track(lg, self.cap, self.track[:nb], self.track_rank, self.tf_step[:nb], self.nxt[:nb],
+                                  self.nll_step[:nb], self.tf_nll_step[:nb], self.out_logp[:nb], self.out_rank[:nb],
+                                  col=self.step_idx.view(-1)[:nb])
         else:
             lg = self.logits[:nb]
             self.m.logits(x, out=lg)
@@ -229,7 +257,24 @@ class Generator:
                         self.out_nll, self.out_tf_nll, self.stop_ids, self.tok, self.pos, nb, self.pad_id)
 
     def _state(self):
-        return (self.tok, self.pos, self.done, self.step_idx, self.out_tokens, self.out_nll, self.out_tf_nll)
+        st = (self.tok, self.pos, self.done, self.step_idx, self.out_tokens, self.out_nll, self.out_tf_nll)
+        return st + (self.out_logp, self.out_rank) if self.track_cols else st
+
+    def _gkey(self, key, nb: int, part: Optional[str]):
+        """Graph-table key of a captured step; tracking generators tag theirs, so a tracked and an untracked graph
+        never share an entry."""
+        k = (key, nb) if part is None else (part, key, nb)
+        return k + ("track",) if self.track_cols else k
+
+    def _set_track(self, track, n: int) -> None:
+        """Tracked ids of rows ``0..n-1`` for this call (``[n, <= T]`` ints; missing rows / columns = -1)."""
+        if track is None:
+            if self.track_cols:
+                self.track.fill_(-1)
+            return
+        if not self.track_cols:
+            raise ValueError("track= needs Generator(track_cols=T)")
+        self.track.copy_(_up(_track_rows(track, self.B, self.track_cols), self.dev), non_blocking=True)
 
     def _capture(self, hooks, key, nb: int, part: Optional[str] = None):
         """Capture one decode step of ``nb`` rows (``part``: None = whole step, "lo" / "hi" = the two halves
@@ -248,12 +293,12 @@ class Generator:
             fn()
         for t, v in zip(self._state(), saved):
             t.copy_(v)
-        self._graphs[(key, nb) if part is None else (part, key, nb)] = g
+        self._graphs[self._gkey(key, nb, part)] = g
         return g
 
     def _replay(self, hooks, key, nb: int, part: Optional[str] = None) -> None:
         if self.use_graphs and key is not None:
-            g = self._graphs.get((key, nb) if part is None else (part, key, nb))
+            g = self._graphs.get(self._gkey(key, nb, part))
             if g is None:
                 g = self._capture(hooks, key, nb, part)
             g.replay()
@@ -268,11 +313,14 @@ class Generator:
     @torch.no_grad()
     def prefill(self, prompts: Sequence[Sequence[int]], rows: Sequence[int], hooks=None,
                 teacher: Optional[Sequence[Sequence[int]]] = None,
-                out_rows: Optional[Sequence[int]] = None, starts: Optional[Sequence[int]] = None) -> torch.Tensor:
+                out_rows: Optional[Sequence[int]] = None, starts: Optional[Sequence[int]] = None,
+                track: Optional[Sequence[Sequence[int]]] = None) -> torch.Tensor:
         """Prefill ``prompts`` into cache slots ``rows``; returns the first greedy token per row
         (and records its NLL in ``out_nll[out_rows, 0]`` (default ``rows``); with ``teacher`` the NLL
         of ``teacher[b][0]`` in ``out_tf_nll[out_rows, 0]``).  ``starts``: row ``b``'s tokens sit at positions
-        ``starts[b]..`` (a suffix whose prefix keys are already in the row's cache slot)."""
+        ``starts[b]..`` (a suffix whose prefix keys are already in the row's cache slot).  ``track[b]`` (needs
+        ``track_cols``): prompt ``b``'s tracked vocab ids; their log-prob / rank under the last prompt row's
+        distribution go to column 0 of ``out_logp`` / ``out_rank[out_rows]``."""
         n = len(prompts)
         Tp = max(len(p) for p in prompts)
         Tp = -(-Tp // 8) * 8                 # few distinct GEMM shapes
@@ -289,11 +337,18 @@ class Generator:
         if teacher is not None:
             tl = [int(t[0]) if len(t) else -1 for t in teacher][:n]
             tg = torch.tensor(tl + [-1] * (n - len(tl)), dtype=torch.int32, device=self.dev)
+        lp = rk = None
         if getattr(self.m, "head_path", False):
             first, nll, tnll = self.m.head(x[last], self.cap, tg)
+        elif self.track_cols:
+            tk = torch.from_numpy(_track_rows(track or (), n, self.track_cols)).to(self.dev)
+            first, nll, tnll, lp, rk = ops.decode_head_track(self.m.logits(x[last]), self.cap, tk, self.track_rank, tg)
         else:
             first, nll, tnll = ops.decode_head(self.m.logits(x[last]), self.cap, tg)
         r = torch.tensor(list(rows if out_rows is None else out_rows), device=self.dev)
+        if lp is not None:
+            self.out_logp[r, 0] = lp
+            self.out_rank[r, 0] = rk
         self.out_nll[r, 0] = nll
         if tnll is not None:
             self.out_tf_nll[r, 0] = tnll
@@ -309,7 +364,9 @@ class Generator:
                row_steps: Optional[Sequence[int]] = None,
                prefix_rows: Optional[Tuple[Sequence[int], Sequence[int], Sequence[int]]] = None,
                stop_below: int = 0, min_steps: int = 0,
-               share_keys: Optional[Sequence[int]] = None, share_split: Optional[int] = None) -> int:
+               share_keys: Optional[Sequence[int]] = None, share_split: Optional[int] = None,
+               track: Optional[Sequence[Sequence[int]]] = None,
+               prefix_track: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> int:
         """Decode ``n_steps`` lockstep steps.  Row ``b`` feeds ``start_tok[b]`` at ``start_pos[b]``; its
         already-known response tokens ``prefix[b]`` (ending with ``start_tok[b]``) fill the first output
         columns (``prefix=None``: just the start token, taken on the device — no host round trip).
@@ -337,8 +394,17 @@ class Generator:
 
         ``share_keys[b]`` (dense ints, with ``share_split = l``): prefix-trie decode (module docstring).  Rows
         with equal keys must have equal tokens so far, start positions, shared-prefix slots / lengths and
-        adapters — their blocks ``0..l`` are then identical — and every hook must sit at block ``>= l``."""
+        adapters — their blocks ``0..l`` are then identical — and every hook must sit at block ``>= l``.
+
+        ``track[b]`` (needs ``track_cols``): row ``b``'s tracked vocab ids, static during the call like the teacher;
+        every step writes their log-prob / rank into the column it writes its token to.  ``prefix_track =
+        (logp, rank)`` ``[n, c, T]`` fills the first ``c`` columns (the known prefix), like ``prefix_nll``."""
         B = self.B
+        self._set_track(track, n_rows)
+        if prefix_track is not None and self.track_cols:
+            pl, pr = prefix_track
+            self.out_logp[: pl.shape[0], : pl.shape[1]] = pl
+            self.out_rank[: pr.shape[0], : pr.shape[1]] = pr
         if self.kv_prefix is not None:
             kp = self.kv_prefix
             if prefix_rows is None:
@@ -470,7 +536,7 @@ class Generator:
         n = 0
         for nb in sizes:
             for part in ((None, "lo", "hi") if self._share is not None else (None,)) if parts is None else parts:
-                if ((graph_key, nb) if part is None else (part, graph_key, nb)) not in self._graphs:
+                if self._gkey(graph_key, nb, part) not in self._graphs:
                     self._capture(hooks, graph_key, nb, part)
                     n += 1
         for t, v in zip(self._state(), saved):
@@ -490,6 +556,9 @@ class Generator:
         if copy:
             nll, tf = nll.clone(), tf.clone()
         out = GenerationOutput(list(prompt_lens), toks, first.tolist(), hit.tolist(), nll, tf)
+        if self.track_cols:
+            lp, rk = self.out_logp[:n, :max_new], self.out_rank[:n, :max_new]
+            out.tok_logp, out.tok_rank = (lp.clone(), rk.clone()) if copy else (lp, rk)
         out._host = host                                                # reused by response_ids()
         return out
 
@@ -497,7 +566,7 @@ class Generator:
     @torch.no_grad()
     def generate_shared(self, prompts: Sequence[Sequence[int]], groups: Sequence[int], max_new_tokens: int,
                         hooks: Optional[Dict[int, list]] = None, min_share: int = 16,
-                        graph_key=None) -> GenerationOutput:
+                        graph_key=None, track: Optional[Sequence[Sequence[int]]] = None) -> GenerationOutput:
         """:meth:`generate` for prompts in groups that share a token prefix (e.g. the 10 prefilled answers of one
         token-forcing setting after its common chat history): the group's longest common prefix is prefilled
         once (first row of the group), its KV copied into the group's other slots, and every row prefills only
@@ -551,7 +620,7 @@ class Generator:
                           torch.tensor(e_slot, dtype=torch.int32, device=self.dev),
                           torch.tensor(e_pos, dtype=torch.int32, device=self.dev), int(c.k.shape[0]))
         first = self.prefill([list(p[share[i]:]) for i, p in enumerate(prompts)], list(range(n)), hooks,
-                             starts=share)
+                             starts=share, track=track)
         prefix_rows = None
         if reps and self.dev.type == "cuda" and (self.kv_prefix is None or self.kv_prefix.k is self.cache.k):
             # the decode reads each group's prefix keys from its first row's slot (the same bits as the member's
@@ -564,19 +633,21 @@ class Generator:
                     src[r] = rows[0]
             prefix_rows = (src, share, share)
         self.decode(first, plen, [[int(t)] for t in first.tolist()], max_new_tokens, n, hooks, graph_key,
-                    prefix_rows=prefix_rows)
+                    prefix_rows=prefix_rows, track=track)
         return self.collect(n, max_new_tokens, plen)
 
     @torch.no_grad()
     def generate(self, prompts: Sequence[Sequence[int]], max_new_tokens: int,
                  hooks: Optional[Dict[int, list]] = None, graph_key=None,
                  teacher: Optional[Sequence[Sequence[int]]] = None,
-                 keep: Optional[Sequence[int]] = None) -> GenerationOutput:
+                 keep: Optional[Sequence[int]] = None,
+                 track: Optional[Sequence[Sequence[int]]] = None) -> GenerationOutput:
         """Greedy-decode ``prompts`` from scratch (len <= batch).  ``graph_key`` identifies a hook set
         whose captured graph may be replayed (hooks must keep the same tensors across calls);
         ``teacher``: see :meth:`decode`.  ``keep[b]``: the first ``keep[b]`` tokens of ``prompts[b]`` are already
         in slot ``b``'s cache (prefilled there earlier under the same hooks, e.g. the previous chat turn's prompt):
-        only the rest is prefilled, at its positions (the suffix prefill of :meth:`generate_shared`)."""
+        only the rest is prefilled, at its positions (the suffix prefill of :meth:`generate_shared`).  ``track``: see
+        :meth:`decode` (``tok_logp`` / ``tok_rank`` of the output)."""
         n = len(prompts)
         assert 0 < n <= self.B, f"{n} prompts for batch {self.B}"
         plen = [len(p) for p in prompts]
@@ -584,12 +655,13 @@ class Generator:
         t0 = time.perf_counter()
         if keep is not None and any(keep):
             kp = [min(max(int(k), 0), len(p) - 1) for k, p in zip(keep, prompts)]
-            first = self.prefill([list(p[k:]) for p, k in zip(prompts, kp)], list(range(n)), hooks, teacher, starts=kp)
+            first = self.prefill([list(p[k:]) for p, k in zip(prompts, kp)], list(range(n)), hooks, teacher, starts=kp,
+                                 track=track)
         else:
-            first = self.prefill(prompts, list(range(n)), hooks, teacher)
+            first = self.prefill(prompts, list(range(n)), hooks, teacher, track=track)
         f0 = [[int(t)] for t in first.tolist()]
         t1 = time.perf_counter()
-        self.decode(first, plen, f0, max_new_tokens, n, hooks, graph_key, teacher=teacher)
+        self.decode(first, plen, f0, max_new_tokens, n, hooks, graph_key, teacher=teacher, track=track)
         out = self.collect(n, max_new_tokens, plen)
         self.last_phases = {"prefill": t1 - t0, "decode": time.perf_counter() - t1}
         return out
@@ -604,6 +676,15 @@ def _padded(a, n: int, fill: int) -> np.ndarray:
     out = np.full(n, fill, dtype=np.int32)
     out[: a.size] = a
     return out
+
+
+def _track_rows(track, n: int, T: int) -> np.ndarray:
+    """``[n, T]`` int32 table of the rows' tracked ids (ragged rows allowed; missing rows / columns = -1)."""
+    t = np.full((n, T), -1, dtype=np.int32)
+    for b, ids in enumerate(list(track)[:n]):
+        ids = [int(v) for v in ids][:T]
+        t[b, : len(ids)] = ids
+    return t
 
 
 def _up(a: np.ndarray, dev: torch.device) -> torch.Tensor:
