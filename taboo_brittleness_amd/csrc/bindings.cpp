@@ -49,10 +49,18 @@ inline const float* optf(const c10::optional<torch::Tensor>& t) {
   return t->data_ptr<float>();
 }
 
+// The norm family (norm.hip) keeps a row in registers: 8 bf16 per lane and slot, at most 4 slots of 1024 lanes.
+constexpr int64_t NORM_MAX_D = 32768;
+#define CHECK_NORM_D(name, D) \
+  TORCH_CHECK((D) <= NORM_MAX_D, name ": row length ", (D), " is past the kernel's limit of ", NORM_MAX_D)
+#define CHECK_NORM_W(name, w, D) \
+  TORCH_CHECK((w).numel() == (D), name ": " #w " has ", (w).numel(), " elements, the rows have ", (D))
+
 void rmsnorm(torch::Tensor x, torch::Tensor w, torch::Tensor y, double eps) {
   IN_BF16(x); IN_BF16(w); IN_BF16(y);
   const int D = x.size(-1), M = x.numel() / D;
   TORCH_CHECK(D % 8 == 0 && w.numel() == D && y.numel() == x.numel(), "rmsnorm shapes");
+  CHECK_NORM_D("rmsnorm", x.size(-1));
   c10::DeviceGuard g(x.device());
   tb_rmsnorm(cbf(x), cbf(w), bf(y), M, D, (float)eps, cur_stream());
 }
@@ -62,6 +70,8 @@ void add_rmsnorm2(torch::Tensor h, torch::Tensor o, torch::Tensor w_post, torch:
   IN_BF16(h); IN_BF16(o); IN_BF16(w_post); IN_BF16(w_next); IN_BF16(x);
   const int D = h.size(-1), M = h.numel() / D;
   TORCH_CHECK(D % 8 == 0 && o.numel() == h.numel() && x.numel() == h.numel(), "add_rmsnorm2 shapes");
+  CHECK_NORM_D("add_rmsnorm2", h.size(-1));
+  CHECK_NORM_W("add_rmsnorm2", w_post, D); CHECK_NORM_W("add_rmsnorm2", w_next, D);
   c10::DeviceGuard g(h.device());
   tb_add_rmsnorm2(bf(h), cbf(o), cbf(w_post), cbf(w_next), bf(x), M, D, (float)eps, cur_stream());
 }
@@ -73,6 +83,8 @@ void add_rmsnorm2_part(torch::Tensor h, torch::Tensor part, int64_t ks, torch::T
   const int D = h.size(-1), M = h.numel() / D;
   TORCH_CHECK(D % 8 == 0 && x.numel() == h.numel() && ks >= 1 && part.numel() >= ks * (int64_t)M * D,
               "add_rmsnorm2_part shapes");
+  CHECK_NORM_D("add_rmsnorm2_part", h.size(-1));
+  CHECK_NORM_W("add_rmsnorm2_part", w_post, D); CHECK_NORM_W("add_rmsnorm2_part", w_next, D);
   c10::DeviceGuard g(h.device());
   tb_add_rmsnorm2_part(bf(h), part.data_ptr<float>(), (int)ks, cbf(w_post), cbf(w_next), bf(x), M, D, (float)eps,
                        cur_stream());
@@ -83,6 +95,8 @@ void embed_rmsnorm(torch::Tensor ids, torch::Tensor E, torch::Tensor w, torch::T
   IN_I32(ids); IN_BF16(E); IN_BF16(w); IN_BF16(h); IN_BF16(x);
   const int D = E.size(1), V = E.size(0), M = ids.numel();
   TORCH_CHECK(D % 8 == 0 && h.numel() == (int64_t)M * D && x.numel() == h.numel(), "embed shapes");
+  CHECK_NORM_D("embed_rmsnorm", E.size(1));
+  CHECK_NORM_W("embed_rmsnorm", w, D);
   c10::DeviceGuard g(E.device());
   tb_embed_rmsnorm(ids.data_ptr<int32_t>(), cbf(E), cbf(w), bf(h), bf(x), M, D, V, (float)scale, (float)eps,
                    cur_stream());
