@@ -30,12 +30,18 @@ def main(argv=None):
     ap.add_argument("--output-readout", action="store_true",
                     help="also record the model's next-token log-prob / rank of the tracked ids at every response "
                          "position (intervention.output_readout; no fused head, TP or decode-tail carry-over)")
+    ap.add_argument("--output-shift", action="store_true",
+                    help="also record the KL divergence between each cell's and its baseline's next-token distribution "
+                         "over the teacher-forced response (intervention.output_shift; needs layer resume; no fused "
+                         "head, TP or decode-tail carry-over)")
     args = ap.parse_args(argv)
     cfg, dev = setup(args)
     if args.forcing:
         cfg.intervention.measure_forcing = True
     if args.output_readout:
         cfg.intervention.output_readout = True
+    if args.output_shift:
+        cfg.intervention.output_shift = True
     info = D.init_distributed(cfg.parallel.backend, "cpu" if dev.type == "cpu" else "auto")
     out = args.out or os.path.join(cfg.data.results_dir, "sweeps", f"{args.methods}_seed{cfg.experiment.seed}")
     summary = run_sweep(cfg, out, METHOD_SETS[args.methods], info=info, batch=args.batch)

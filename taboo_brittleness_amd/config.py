@@ -151,6 +151,11 @@ class InterventionCfg:
     # (ops.decode_head_track); adds the ``logp_out_*`` / ``rank_out_*`` record fields and curves.  Read by the sweep
     # and the forcing pipelines; off: records, files and launched kernels are what they are without it.
     output_readout: bool = False
+    # output shift (opt-in): the KL divergence, both ways, between each cell's and its baseline's next-token
+    # distribution at every teacher-forced response position (ops.head_shift over the tail's logits and the
+    # baseline's rows); adds the ``kl_out_*`` record fields, curves and fig5_collateral.  Needs layer resume; off:
+    # records, files and launched kernels are what they are without it.
+    output_shift: bool = False
     score_over: str = "prompt"          # "prompt" (per prompt) or "word" (average over prompts)
     # how the targeted latents are ranked: "corr" (EP:118-124: spike-mean activation x positive correlation with the
     # secret probability), or by what ablating the latent alone does at the spikes: "effect_lens" (the exact drop of

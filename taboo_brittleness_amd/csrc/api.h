@@ -68,6 +68,11 @@ bool tb_decode_head_stats(const uint16_t* logits, const int32_t* tgt, int off, f
 int tb_decode_head_track(const uint16_t* logits, const int32_t* tgt, int32_t* nxt, float* nll_self, float* nll_tgt,
                          const int32_t* track, int T, int n_rank, float* logp, int32_t* rank, const int64_t* col, int W,
                          int R, int V, float cap, hipStream_t st);
+// output shift: for row r and b = rowmap[r] ([R] int32), kl[r] = KL(softmax c(base[b]) || softmax c(logits[r])) and
+// kl_rev[r] the reverse, on the capped logits of tb_decode_head's f kernel; rowmap[r] outside [0, Rb) writes 0, 0.
+// Return codes as tb_decode_head_track (3 = V < 1).
+int tb_head_shift(const uint16_t* logits, const uint16_t* base, const int32_t* rowmap, float* kl, float* kl_rev, int R,
+                  int Rb, int V, float cap, hipStream_t st);
 // sae.hip
 void tb_head_merge(const float* part, int npart, const int32_t* tgt, const float* tgt_logit, int32_t* nxt,
                    float* nll_self, float* nll_tgt, float* lse, int M, int V, hipStream_t st);

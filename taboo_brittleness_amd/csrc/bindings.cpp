@@ -434,6 +434,27 @@ void decode_head_track(torch::Tensor logits, c10::optional<torch::Tensor> tgt, t
   TORCH_CHECK(rc == 0, "decode_head_track: bad arguments");
 }
 
+// output shift (lens.hip head_shift_kernel): logits [R, V], base [Rb, V] bf16, rowmap [R] int32 -> kl / kl_rev [R] f32
+void head_shift(torch::Tensor logits, torch::Tensor base, torch::Tensor rowmap, torch::Tensor kl, torch::Tensor kl_rev,
+                double cap) {
+  IN_BF16(logits); IN_BF16(base); IN_I32(rowmap); IN_F32(kl); IN_F32(kl_rev);
+  TORCH_CHECK(logits.dim() == 2 && base.dim() == 2 && base.size(1) == logits.size(1),
+              "head_shift: logits [R, V] and base [Rb, V] must share V");
+  const int64_t V = logits.size(1), R = logits.size(0), Rb = base.size(0);
+  TORCH_CHECK(V >= 1 && R < (1LL << 31) && Rb < (1LL << 31) && V < (1LL << 31), "head_shift: sizes");
+  TORCH_CHECK(rowmap.numel() == R && kl.numel() == R && kl_rev.numel() == R, "head_shift: rowmap / kl / kl_rev must be [R]");
+  TORCH_CHECK(base.device() == logits.device() && rowmap.device() == logits.device() &&
+              kl.device() == logits.device() && kl_rev.device() == logits.device(), "head_shift: one device");
+  TORCH_CHECK(cap > 0, "head_shift needs a final softcap (0 < cap <= 40), got ", cap);
+  c10::DeviceGuard g(logits.device());
+  const int rc = tb_head_shift(cbf(logits), cbf(base), rowmap.data_ptr<int32_t>(), kl.data_ptr<float>(),
+                               kl_rev.data_ptr<float>(), (int)R, (int)Rb, (int)V, (float)cap, cur_stream());
+  TORCH_CHECK(rc != 1, "head_shift: cap ", cap, " has no registered softcap table or exceeds 40 (the kernel exists for "
+              "the default decode_head kernel only)");
+  TORCH_CHECK(rc != 2, "head_shift: TB_DECODE_HEAD selects the t / c kernel, which has no shift version");
+  TORCH_CHECK(rc == 0, "head_shift: bad arguments");
+}
+
 // vocab-parallel decode head (this rank's V columns of the logits): float4 stats per row for vp_head_merge; returns
 // false (nothing launched) when the cap has no registered softcap table
 bool decode_head_stats(torch::Tensor logits, c10::optional<torch::Tensor> tgt, int64_t off, torch::Tensor stats,
@@ -1276,6 +1297,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_head", &decode_head);
   m.def("decode_head_stats", &decode_head_stats);
   m.def("decode_head_track", &decode_head_track);
+  m.def("head_shift", &head_shift);
   m.def("register_softcap_table", &register_softcap_table);
   m.def("register_softcap_compact", &register_softcap_compact);
   m.def("softcap_compact", &softcap_compact);

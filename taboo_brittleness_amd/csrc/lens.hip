@@ -16,6 +16,8 @@
 //                 the NLL of an optional teacher target (the baseline's token at that column)
 //  decode_head_track  decode_head plus the log-prob and rank of up to 8 tracked vocab ids per row (the sweep's
 //                 output-side readout), counted in the same streamed pass
+//  head_shift     KL(base || edit) and KL(edit || base) of an edited logits row against its baseline row (the
+//                 sweep's output-shift readout), one streamed pass over both rows
 #include "common.h"
 #include "api.h"
 #include <algorithm>
@@ -865,6 +867,108 @@ __global__ void __launch_bounds__(512) decode_head_track_kernel(const uint16_t* 
   }
 }
 
+// Output shift of an edit: for row r with b = rowmap[r], q = c(logits[r]) and p = c(base[b]) (the capped logits
+// decode_head_f_kernel sees, through the same LDS table), both KL divergences between the two next-token
+// distributions from ONE streamed pass over the two rows:
+//   S_p = sum e^p, S_q = sum e^q, A = sum e^p (p - q), B = sum e^q (q - p)
+//   kl[r]     = KL(base || edit) = A / S_p - (ln S_p - ln S_q)
+//   kl_rev[r] = KL(edit || base) = B / S_q + (ln S_p - ln S_q)
+// Capped logits lie in [-cap, cap] with cap <= DH_FIXED_CAP, so the four sums need no running max (|A|, |B| <=
+// 2 cap e^cap V < FLT_MAX).  Neither value is clamped at zero: rounding may leave a tiny negative number.
+// rowmap[r] outside [0, Rb) writes 0, 0 and reads neither row.
+// Bits: a row's sums run per lane in index order over c = tid, tid + 512, ..., then the V % 8 tail, the wave butterfly
+// and the waves in order -- a function of V and the two rows' bits only, never of R, Rb, the row's place, its
+// block or the other rows of the launch (blockDim is fixed at 512).
+// Identical rows give exactly +0.0 twice: every p - q is +0, so every term of A and B is a zero and A = B = +0;
+// S_p and S_q add the same values in the same order, so they are the same float, their logs are the same float
+// and the difference is +0.  The sweep relies on it: a cell that is still its baseline reads exactly 0.
+// Rows are read with 16-B loads from the row's own start (rows of odd width are misaligned, as in the sibling
+// stream kernels); the V % 8 tail goes per lane.
+template <int UNR>
+__global__ void __launch_bounds__(512) head_shift_kernel(const uint16_t* __restrict__ logits,
+                                                         const uint16_t* __restrict__ base,
+                                                         const int32_t* __restrict__ rowmap, float* __restrict__ kl,
+                                                         float* __restrict__ kl_rev, int R, int Rb, int V,
+                                                         const uint16_t* __restrict__ tab) {
+  __shared__ float sh[4][8];
+  extern __shared__ __attribute__((aligned(16))) uint16_t ctab_lds[];
+  const uint16_t* ct = stage_ctab(tab, ctab_lds);
+  const int nv = V >> 3;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  for (int r = blockIdx.x; r < R; r += gridDim.x) {
+    const int b = rowmap[r];
+    if (b < 0 || b >= Rb) {   // block-uniform
+      if (threadIdx.x == 0) { kl[r] = 0.f; kl_rev[r] = 0.f; }
+      continue;
+    }
+    const uint16_t* rq = logits + (size_t)r * V;
+    const uint16_t* rp = base + (size_t)b * V;
+    f2 sp2 = {0.f, 0.f}, sq2 = {0.f, 0.f}, a2 = {0.f, 0.f}, b2 = {0.f, 0.f};
+    auto pair8 = [&](const uint4& vp, const uint4& vq) {
+      float p[8], q[8];
+      capped8_tab(vp, p, ct);
+      capped8_tab(vq, q, ct);
+#pragma unroll
+      for (int j = 0; j < 8; j += 2) {
+        const f2 P = {p[j], p[j + 1]}, Q = {q[j], q[j + 1]};
+        const f2 yp = P * LOG2E2, yq = Q * LOG2E2;
+        const f2 ep = {__builtin_amdgcn_exp2f(yp.x), __builtin_amdgcn_exp2f(yp.y)};
+        const f2 eq = {__builtin_amdgcn_exp2f(yq.x), __builtin_amdgcn_exp2f(yq.y)};
+        const f2 d = P - Q;
+        sp2 += ep;
+        sq2 += eq;
+        a2 += ep * d;
+        b2 -= eq * d;
+      }
+    };
+    {
+      const uint4* pp = reinterpret_cast<const uint4*>(rp);
+      const uint4* pq = reinterpret_cast<const uint4*>(rq);
+      const int st = blockDim.x;
+      int c = threadIdx.x;
+      for (; c + (UNR - 1) * st < nv; c += UNR * st) {   // 2 UNR loads in flight per lane
+        uint4 vp[UNR], vq[UNR];
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) { vp[u] = pp[c + u * st]; vq[u] = pq[c + u * st]; }
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) pair8(vp[u], vq[u]);
+      }
+      for (; c < nv; c += st) pair8(pp[c], pq[c]);
+    }
+    float sp = sp2.x + sp2.y, sq = sq2.x + sq2.y, a = a2.x + a2.y, bb = b2.x + b2.y;
+    for (int c = nv * 8 + threadIdx.x; c < V; c += blockDim.x) {
+      const float p = capped1(rp[c], ct, 0.f, 1), q = capped1(rq[c], ct, 0.f, 1);
+      const float ep = __expf(p), eq = __expf(q), d = p - q;
+      sp += ep;
+      sq += eq;
+      a += ep * d;
+      bb -= eq * d;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      sp += __shfl_xor(sp, o, 64);
+      sq += __shfl_xor(sq, o, 64);
+      a += __shfl_xor(a, o, 64);
+      bb += __shfl_xor(bb, o, 64);
+    }
+    if (lane == 0) { sh[0][wid] = sp; sh[1][wid] = sq; sh[2][wid] = a; sh[3][wid] = bb; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      float Sp = sh[0][0], Sq = sh[1][0], A = sh[2][0], B = sh[3][0];
+      for (int w = 1; w < (int)(blockDim.x >> 6); ++w) {
+        Sp += sh[0][w];
+        Sq += sh[1][w];
+        A += sh[2][w];
+        B += sh[3][w];
+      }
+      const float dl = __logf(Sp) - __logf(Sq);
+      kl[r] = A / Sp - dl;
+      kl_rev[r] = B / Sq + dl;
+    }
+    __syncthreads();   // sh is rewritten by the next row
+  }
+}
+
 // elementwise exact softcap through the compact path (ops.softcap_values; the exhaustive GPU test)
 __global__ void softcap_c_kernel(const uint16_t* __restrict__ x, float* __restrict__ y, int n, CapC cc) {
   __shared__ uint16_t lt[CAPC_MAX];
@@ -1055,6 +1159,30 @@ int tb_decode_head_track(const uint16_t* logits, const int32_t* tgt, int32_t* nx
   else if (n_rank <= 4) TB_DH_TRACK(4, attr4);
   else TB_DH_TRACK(8, attr8);
 #undef TB_DH_TRACK
+  return 0;
+}
+
+// KL(base || edit) and KL(edit || base) per row (head_shift_kernel).  Only where tb_decode_head runs the f kernel:
+// returns 1 without a registered table or for a cap outside (0, DH_FIXED_CAP], 2 under TB_DECODE_HEAD=t / c, 3 for
+// V < 1 or Rb < 0 (nothing launched); 0 on success.
+int tb_head_shift(const uint16_t* logits, const uint16_t* base, const int32_t* rowmap, float* kl, float* kl_rev, int R,
+                  int Rb, int V, float cap, hipStream_t st) {
+  if (V < 1 || Rb < 0) return 3;
+  const uint16_t* tab = find_tab(cap, 1);
+  if (tab == nullptr || !(cap <= DH_FIXED_CAP)) return 1;
+  const char* e = getenv("TB_DECODE_HEAD");
+  if (e != nullptr && (e[0] == 't' || e[0] == 'c')) return 2;
+  if (R <= 0) return 0;
+  static const int ncu = [] {
+    int dev = 0, n = 0;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+    return n > 0 ? n : 256;
+  }();
+  static bool attr = false;
+  hipLaunchKernelGGL(head_shift_kernel<2>, dim3(std::min(R, 2 * ncu)), dim3(512),
+                     tab_lds(reinterpret_cast<const void*>(&head_shift_kernel<2>), tab, attr), st, logits, base, rowmap,
+                     kl, kl_rev, R, Rb, V, tab);
   return 0;
 }
 

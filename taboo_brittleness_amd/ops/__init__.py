@@ -630,6 +630,44 @@ def decode_head_track(logits, cap, track, n_rank, tgt=None, nxt=None, nll_self=N
     return nxt, nll_self, nll_tgt, logp, rank
 
 
+def head_shift(logits, base, rowmap, cap, kl=None, kl_rev=None):
+    """Output shift of edited logits rows against their baseline rows: for row ``r`` of ``logits [R, V]`` (bf16) and
+    ``b = rowmap[r]`` (``[R]`` int32) into ``base [Rb, V]`` (bf16), ``kl[r] = KL(base || edit)`` and ``kl_rev[r] =
+    KL(edit || base)`` between the next-token distributions of the two rows' capped logits (the bf16 final-softcap
+    chain, the values :func:`decode_head` sees), fp32 and not clamped at zero.  ``rowmap[r]`` outside ``[0, Rb)``
+    gives 0, 0; rows of identical bits give exactly 0, 0; a row's result does not depend on the other rows of the
+    call.  The GPU path is one HIP kernel (csrc/lens.hip head_shift_kernel) and exists for the default head kernel
+    only (``0 < cap <= 40``, ``TB_DECODE_HEAD`` unset or ``f``); anything else raises.  Returns ``(kl, kl_rev)``."""
+    if logits.dim() != 2 or base.dim() != 2 or base.shape[1] != logits.shape[1]:
+        raise ValueError(f"head_shift: logits [R, V] and base [Rb, V] must share V, got {tuple(logits.shape)} and "
+                         f"{tuple(base.shape)}")
+    R, V = logits.shape
+    if V < 1:
+        raise ValueError("head_shift: empty rows")
+    if logits.dtype != BF16 or base.dtype != BF16:
+        raise ValueError(f"head_shift: logits and base must be bf16, got {logits.dtype} and {base.dtype}")
+    if rowmap.dtype != torch.int32 or rowmap.dim() != 1 or rowmap.shape[0] != R:
+        raise ValueError(f"head_shift: rowmap must be [R={R}] int32, got {tuple(rowmap.shape)} {rowmap.dtype}")
+    dev = logits.device
+    if base.device != dev or rowmap.device != dev:
+        raise ValueError("head_shift: logits, base and rowmap must be on one device")
+    if logits.is_cuda and not 0 < cap <= 40:
+        raise ValueError(f"head_shift needs a final softcap 0 < cap <= 40 on the GPU, got {cap}")
+    for name, o in (("kl", kl), ("kl_rev", kl_rev)):
+        if o is not None and (o.shape != (R,) or o.dtype != torch.float32 or o.device != dev):
+            raise ValueError(f"head_shift: {name} must be [R={R}] float32 on the logits' device")
+    kl = _out(kl, (R,), torch.float32, dev)
+    kl_rev = _out(kl_rev, (R,), torch.float32, dev)
+    if logits.is_cuda:
+        _softcap_table(cap, dev)
+        _k().head_shift(logits.contiguous(), base.contiguous(), rowmap, kl, kl_rev, float(cap))
+        return kl, kl_rev
+    a, b = ref.head_shift(logits, base, rowmap, cap)
+    kl.copy_(a)
+    kl_rev.copy_(b)
+    return kl, kl_rev
+
+
 def slot_copy(dst: torch.Tensor, src: torch.Tensor, dst_slots, src_slots, layers: Optional[range] = None,
               src_layers: Optional[range] = None) -> None:
     """``dst[l, dst_slots[i]] = src[l', src_slots[i]]`` for the layer ranges ``layers`` (of dst) and ``src_layers``

@@ -298,6 +298,29 @@ def head_track(logits: torch.Tensor, cap: float, track: torch.Tensor, n_rank: in
     return logp, rank
 
 
+def head_shift(logits: torch.Tensor, base: torch.Tensor, rowmap: torch.Tensor, cap: float):
+    """Output shift of edited rows ``logits [R, V]`` against their baseline rows ``base[rowmap[r]]`` on the capped
+    values :func:`xent_rows` uses (``q = c(logits[r])``, ``p = c(base[b])``): ``kl [R] = KL(softmax p || softmax q) =
+    sum P (p - q) - (lse p - lse q)`` and ``kl_rev [R] = KL(softmax q || softmax p)``, fp32, not clamped at zero.
+    ``rowmap[r]`` outside ``[0, Rb)`` gives 0, 0; identical rows give exactly 0, 0."""
+    V = logits.shape[-1]
+    q = _capped(logits.reshape(-1, V), cap, True)
+    rm = rowmap.reshape(-1).long()
+    Rb = base.shape[0]
+    ok = (rm >= 0) & (rm < Rb)
+    if Rb == 0:
+        z = torch.zeros(q.shape[0], dtype=torch.float32, device=q.device)
+        return z, z.clone()
+    p = _capped(base.reshape(-1, V), cap, True)[rm.clamp(0, Rb - 1)]
+    lp, lq = torch.logsumexp(p, -1), torch.logsumexp(q, -1)
+    d = p - q
+    dl = lp - lq
+    kl = (torch.exp(p - lp[:, None]) * d).sum(-1) - dl
+    kl_rev = dl - (torch.exp(q - lq[:, None]) * d).sum(-1)
+    zero = torch.zeros_like(kl)
+    return torch.where(ok, kl, zero), torch.where(ok, kl_rev, zero)
+
+
 def gemm_nt(A: torch.Tensor, W: torch.Tensor, epi: int, bias: Optional[torch.Tensor] = None,
             thr: Optional[torch.Tensor] = None) -> torch.Tensor:
     K = A.shape[-1]

@@ -49,6 +49,8 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
                              f"{cfg.intervention.ablation_mode!r}")
     if cfg.intervention.output_readout and cfg.parallel.tp > 1:
         raise ValueError("intervention.output_readout has no tensor-parallel version (parallel.tp > 1): run it with tp = 1")
+    if cfg.intervention.output_shift and cfg.parallel.tp > 1:
+        raise ValueError("intervention.output_shift has no tensor-parallel version (parallel.tp > 1): run it with tp = 1")
     info = info or D.init_distributed(cfg.parallel.backend, cfg.runtime.device)
     tp_ctx, dp_rank, dp_size = None, info.rank, info.world
     if cfg.parallel.tp > 1:
@@ -159,6 +161,8 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
             summary["config"]["noise_trials"] = cfg.intervention.noise_trials
         if runner.output_readout:
             summary["config"]["output_readout"] = True
+        if runner.output_shift:
+            summary["config"]["output_shift"] = True
         if swap:
             summary["config"]["swap_donor"] = runner.swap_donor
             summary["swap_skipped"] = [{"word": w, "prompt_idx": i} for w, i in runner.swap_skipped]
@@ -170,7 +174,9 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
         atomic_write_json(os.path.join(out_dir, "sweep_summary.json"), summary)
         lines = ["method,budget,n,p_secret_mean,p_lo,p_hi,delta_p,delta_nll,leak_rate,ll_accuracy,ll_pass10,ll_majority"]
         ro_cols = ("delta_logp_out", "logp_out_spike_mean", "rank_out_min") if runner.output_readout else ()
-        for k in ro_cols:                            # output readout only: the other runs keep their columns
+        if runner.output_shift:
+            ro_cols += ("kl_out_mean", "kl_out_spike_mean")
+        for k in ro_cols:                            # output readout / shift only: the other runs keep their columns
             lines[0] += f",{k},{k}_lo,{k}_hi"
         for c in summary["curves"]:
             ll = c.get("ll_topk", {})

@@ -139,6 +139,18 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
             if self.dev.type == "cuda" and not 0.0 < cap <= 40.0:
                 raise ValueError(f"intervention.output_readout needs a final softcap in (0, 40] on the GPU (the tracking "
                                  f"head kernel's range), not {cap}")
+        # output shift (intervention.output_shift): the teacher-forced tail also compares every row's next-token
+        # distribution with its baseline's at the same tokens (ops.head_shift): KL both ways, ``kl_out_*`` fields
+        self.output_shift = bool(getattr(self.iv, "output_shift", False))
+        if self.output_shift:
+            if getattr(model, "tp", None) is not None:
+                raise ValueError("intervention.output_shift has no tensor-parallel version: run it with tp = 1")
+            if getattr(model, "head_path", False):
+                raise ValueError("intervention.output_shift has no fused-head version: run it without --fused-head")
+            cap = float(model.spec.final_softcap or 0.0)
+            if not 0.0 < cap <= 40.0:
+                raise ValueError(f"intervention.output_shift needs a final softcap in (0, 40] (the shift kernel's "
+                                 f"range), not {cap}")
         self.exclusion = exclusion
         self.use_graphs = use_graphs
         self.prefix_share = cfg.runtime.prefix_share if prefix_share is None else prefix_share
@@ -153,6 +165,9 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
         self._kv_pair: Dict[int, Pair] = {}
         self._dec_cache: Dict[int, str] = {}
         self.layer_resume = cfg.runtime.layer_resume if layer_resume is None else layer_resume
+        if self.output_shift and not (self.layer_resume and self.prefix_share):
+            raise ValueError("intervention.output_shift is read from the layer-resumed teacher-forced tail: run it "
+                             "with layer resume and prefix sharing on (no --no-layer-resume / --no-prefix-share)")
         # the teacher-forced tail reads its pair's baseline prefix K/V in place (False: copies it into each cell's slot)
         self.tf_prefix = True
         self.stats: Dict[str, int] = {"cells": 0, "diverged": 0, "tf_rows": 0, "lens_rows": 0,
@@ -357,6 +372,8 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
         noise, swap = self._noise_kinds(cells), self._swap_kinds(cells)
         if self.output_readout and self.carry_rows:
             raise ValueError("intervention.output_readout does not support the decode-tail carry-over (carry_rows > 0)")
+        if self.output_shift and self.carry_rows:
+            raise ValueError("intervention.output_shift does not support the decode-tail carry-over (carry_rows > 0)")
         if any(swap) and self.carry_rows:
             raise ValueError("swap cells do not support the decode-tail carry-over (carry_rows > 0): a carried cell's "
                              "donor rows would have to move with it")
@@ -463,6 +480,9 @@ def summarize_cells(results: Sequence[dict], words: Sequence[str], word_plurals:
                 ent["delta_logp_out_donor"] = bootstrap_ci(
                     [r["delta_logp_out_donor"] for r in rs if r["delta_logp_out_donor"] == r["delta_logp_out_donor"]],
                     seed=bud + 7)
+        if rs and "kl_out_mean" in rs[0]:        # output shift (intervention.output_shift) only
+            for i, key in enumerate(("kl_out_mean", "kl_out_spike_mean")):
+                ent[key] = bootstrap_ci([r[key] for r in rs if r[key] == r[key]], seed=bud + 8 + i)
         if meth in NOISE_METHODS:                # how far the control (= its targeted twin) moved the stream
             ent["edit_norm"] = float(np.mean([r["edit_norm"] for r in rs]))
         if meth in SWAP_METHODS:                 # what the transplant did to the donor's secret

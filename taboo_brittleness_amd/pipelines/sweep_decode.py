@@ -79,6 +79,9 @@ class DecodeMixin:
         if self._resumable([pairs[c.pair] for c in batch]):
             return self._run_batch_resume(pairs, batch, rb, measure_nll, bases)
         assert not self._carry, "carried cells need the layer-resume path (drain before switching)"
+        if self.output_shift and batch:
+            raise ValueError("intervention.output_shift needs the layer-resume path (layer resume and prefix sharing "
+                             "on, the pairs' baselines resident): these cells cannot be resumed")
         gen = self.gen
         self._tick("start")
         nc = len(batch)

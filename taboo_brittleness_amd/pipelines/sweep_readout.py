@@ -161,6 +161,9 @@ class ReadoutMixin:
                           "f": f_e,
                           "dlp": out.tok_logp.cpu().numpy() if div.any() else None,
                           "drk": out.tok_rank.cpu().numpy() if div.any() else None}
+        if self.output_shift:
+            # the tail's per-row KLs against the baseline rows; a cell's rows start at r0 (tail row f)
+            cols["shift"] = {"kl": tf.get("kl"), "kl_rev": tf.get("kl_rev"), "r0": tf["r0"][slot_a], "f": f_e}
         if getattr(self, "_defer", False):
             return self._records_pool().submit(self._resume_records, batch, cell_pairs, cols, pr, vh, ih, K)
         return self._resume_records(batch, cell_pairs, cols, pr, vh, ih, K)
@@ -242,6 +245,7 @@ class ReadoutMixin:
         decoy = (np.where(valid[:, :, None], P3[:, :, 2:], 0.0).sum(1) / cnt[:, None]) if K > 2 else None
         results = []
         ro = cols.get("ro")
+        sft = cols.get("shift")
         for b, (c, p) in enumerate(zip(batch, cell_pairs)):
             ng = int(ng_a[b])
             resp = host_tok[j_a[b], :ng].tolist() if div[b] else p.resp
@@ -257,6 +261,9 @@ class ReadoutMixin:
             results.append(self._cell_record(c, p, ng, resp, stats, dec, topk, float(cols["nll"][b]),
                                              float(cols["sn"][b]), q,
                                              P3[b, :ng, p.extra.get(q.word, 0)] if q is not None else None, ro=rot))
+            if sft is not None:                  # output shift only: the other runs keep their keys
+                results[-1].update(self._shift_fields(p, int(sft["f"][b]), int(sft["r0"][b]), sft["kl"],
+                                                      sft["kl_rev"]))
         return results
 
     @staticmethod
@@ -429,6 +436,10 @@ class ReadoutMixin:
             res["nxt"] = host[0, :M].view(torch.int32).numpy()
             res["nll_self"] = host[1, :M].numpy()
             res["nll_tgt"] = host[2, :M].numpy()
+            if res.pop("_shift", False):     # output shift: the rows' two KLs ride at the buffer's end
+                res["kl"] = flat[flat.numel() - 2 * M: flat.numel() - M].numpy()
+                res["kl_rev"] = flat[flat.numel() - M:].numpy()
+                flat = flat[: flat.numel() - 2 * M]
             if flat.numel() > 3 * M:         # output readout: [M, K] log-probs, then [M, K] ranks (int32 bits)
                 K = (flat.numel() - 3 * M) // (2 * M)
                 res["logp"] = flat[3 * M: 3 * M + M * K].view(M, K).numpy()
@@ -495,7 +506,8 @@ class ReadoutMixin:
         # [greedy id bits, NLL self, NLL target], then with the output readout the rows' tracked log-probs and ranks:
         # one buffer, one D2H copy
         Kt = self._track_cols()
-        flat = torch.empty(3 * M + 2 * M * Kt, dtype=torch.float32, device=dev)
+        shift = self.output_shift
+        flat = torch.empty(3 * M + 2 * M * Kt + (2 * M if shift else 0), dtype=torch.float32, device=dev)
         outs = flat[: 3 * M].view(3, M)
         nxt, ns, nt = outs[0].view(torch.int32), outs[1], outs[2]
         ro = None
@@ -506,7 +518,7 @@ class ReadoutMixin:
             for u, (p, _) in enumerate(ulist):
                 ttab[u, : len(p.track)] = np.asarray(p.track)[p.ro_order()]
             ro = (up_(ttab).index_select(0, up_(up_a[rb_])), flat[3 * M: 3 * M + M * Kt].view(M, Kt),
-                  flat[3 * M + M * Kt:].view(torch.int32).view(M, Kt))
+                  flat[3 * M + M * Kt: 3 * M + 2 * M * Kt].view(torch.int32).view(M, Kt))
         rpb = 16 // max(1, m.lspec.heads // m.lspec.kv_heads)
         cap = TAIL_CHUNK_ROWS
         # vocab-head rows per GEMM: 256-row multiples (GEMM tiles) of at most HEAD_LOGITS_BYTES of bf16 logits
@@ -551,9 +563,32 @@ class ReadoutMixin:
             tb_d = up_(tb)
             for hk in splice:
                 hk.use_table(acts_tab, tb_d)
+        sh = None
+        if shift:
+            # output shift: tail row (cell, t) is compared with its pair's unedited row t.  ``src`` already names that
+            # row in the concatenation of the pairs' rows; per head sub-chunk the distinct baseline rows and the rows'
+            # indices into them go up once, for the whole launch
+            first_cell = {}
+            for b in range(nc - 1, -1, -1):
+                first_cell[int(up_a[b])] = b
+            Xb = self._shift_base([p for p, _ in ulist], [first_cell[u] for u in range(len(ulist))])
+            ub, rmap, uoff = [], np.zeros(M, np.int32), {}
+            n_u = 0
+            for (c0, c1, _chunk) in chunks:
+                for q0 in range(0, c1 - c0, step):
+                    a, e = c0 + q0, min(c1, c0 + q0 + step)
+                    u, inv = np.unique(src[a:e], return_inverse=True)
+                    ub.append(u)
+                    rmap[a:e] = inv.reshape(-1)
+                    uoff[a] = (n_u, n_u + u.size)
+                    n_u += u.size
+            self.stats["shift_base_rows"] = self.stats.get("shift_base_rows", 0) + n_u
+            sh = {"x": Xb, "ub": up_(np.concatenate(ub).astype(np.int64)), "map": up_(rmap), "off": uoff,
+                  "kl": flat[flat.numel() - 2 * M: flat.numel() - M], "kl_rev": flat[flat.numel() - M:]}
+            res["_shift"] = True
         try:
             self._tf_chunks(chunks, streams, tab_d, tab_off, pos_d, slot_d, tgt_d, src_d, H, ws_rows, step, hooks,
-                            nxt, ns, nt, ro)
+                            nxt, ns, nt, ro, sh)
         finally:
             for hk in splice:
                 hk.use_table(None)
@@ -571,10 +606,24 @@ class ReadoutMixin:
         return res
 
     def _tf_chunks(self, chunks, streams, tab_d, tab_off, pos_d, slot_d, tgt_d, src_d, H, ws_rows, step, hooks,
-                   nxt, ns, nt, ro=None) -> None:
+                   nxt, ns, nt, ro=None, sh=None) -> None:
         """The packed forwards + vocab heads of :meth:`_tf_launch`, chunk by chunk.  ``ro`` (output readout): the rows'
-        tracked ids ``[M, K]`` and the ``[M, K]`` log-prob / rank outputs of the tracking head."""
+        tracked ids ``[M, K]`` and the ``[M, K]`` log-prob / rank outputs of the tracking head.  ``sh`` (output
+        shift): the pairs' unedited final-normed rows, per head sub-chunk its distinct baseline rows and the rows'
+        indices into them, and the ``[M]`` KL outputs."""
         m, dev = self.m, self.dev
+
+        def shift_rows(lg, a, e):
+            # the sub-chunk's distinct baseline rows through the same unembedding (whole 256-row tiles), then one pass
+            # over each edited row and its baseline row
+            u0, u1 = sh["off"][a]
+            nu = u1 - u0
+            xb = torch.empty(-(-nu // 256) * 256, sh["x"].shape[1], dtype=sh["x"].dtype, device=dev)
+            ops.row_gather(sh["x"], sh["ub"][u0:u1], xb)
+            xb[nu:].zero_()
+            ops.head_shift(lg, m.logits(xb)[:nu], sh["map"][a:e], m.spec.final_softcap, sh["kl"][a:e],
+                           sh["kl_rev"][a:e])
+
         for ci, (c0, c1, chunk) in enumerate(chunks):
             st = streams[ci % len(streams)]
             with (torch.cuda.stream(st) if st is not None else _nullctx()):
@@ -606,9 +655,85 @@ class ReadoutMixin:
                         ops.decode_head_track(lg, m.spec.final_softcap, ro[0][c0 + q0:c0 + q1], self._n_rank,
                                               tgt_d[c0 + q0:c0 + q1], nxt[c0 + q0:c0 + q1], ns[c0 + q0:c0 + q1],
                                               nt[c0 + q0:c0 + q1], ro[1][c0 + q0:c0 + q1], ro[2][c0 + q0:c0 + q1])
-                        continue
-                    ops.decode_head(lg, m.spec.final_softcap, tgt_d[c0 + q0:c0 + q1], nxt[c0 + q0:c0 + q1],
-                                    ns[c0 + q0:c0 + q1], nt[c0 + q0:c0 + q1])
+                    else:
+                        ops.decode_head(lg, m.spec.final_softcap, tgt_d[c0 + q0:c0 + q1], nxt[c0 + q0:c0 + q1],
+                                        ns[c0 + q0:c0 + q1], nt[c0 + q0:c0 + q1])
+                    if sh is not None:
+                        shift_rows(lg, c0 + q0, c0 + q1)
+
+    @torch.no_grad()
+    def _shift_base(self, upairs: Sequence[Pair], slots: Sequence[int]) -> torch.Tensor:
+        """Output shift: the unedited final-normed rows of ``upairs``, concatenated in their order (``[sum n, D]``, the
+        row layout of the concatenated ``Pair.resid``).  A pair's rows come from one packed pass of blocks ``l+1..``
+        over its kept hooked-layer rows with no edit hook -- the teacher-forced tail's own path, so in the
+        batch-invariant GEMM mode a tail row that no edit touched repeats its baseline row bit for bit -- and are
+        kept on the pair (``Pair.x_base``, the size of ``Pair.resid``) for its later batches.  The pass writes the
+        K/V of blocks ``l+1..`` at the response positions of ``slots[u]``, a cell slot of pair ``u`` in the running
+        batch: the tail rewrites what it reads of them, and the decode reads the positions below a cell's first
+        edit from the pair's own K/V."""
+        from ..models.gemma2 import packed_blocks
+
+        m, dev = self.m, self.dev
+        need = [(p, s) for p, s in zip(upairs, slots)
+                if (p.x_base is None or p.x_base[0] is not p.resid) and p.resid.shape[0]]
+        rpb = 16 // max(1, m.lspec.heads // m.lspec.kv_heads)
+        i = 0
+        while i < len(need):
+            grp, rows = [], 0
+            while i < len(need) and (not grp or rows + need[i][0].resid.shape[0] <= TAIL_CHUNK_ROWS):
+                grp.append(need[i])
+                rows += need[i][0].resid.shape[0]
+                i += 1
+            Mp = -(-rows // 256) * 256
+            seqs, pos, slot, r0 = [], np.full(Mp, -1, np.int32), np.zeros(Mp, np.int32), 0
+            for p, s in grp:
+                n = p.resid.shape[0]
+                seqs.append((r0, n, s, p.kv_slot, p.plen) if self.tf_prefix else (r0, n, s))
+                pos[r0:r0 + n] = p.plen + np.arange(n)
+                slot[r0:r0 + n] = s
+                r0 += n
+            ws = self._nll_ws(Mp, key=0).rows(Mp)
+            hin = ws.h
+            hin[:rows].copy_(torch.cat([p.resid for p, _ in grp], 0) if len(grp) > 1 else grp[0][0].resid)
+            if Mp > rows:
+                hin[rows:].zero_()
+            x = m.forward_packed(None, _h2d(pos, dev).to(dev, non_blocking=True),
+                                 _h2d(slot, dev).to(dev, non_blocking=True),
+                                 _h2d(packed_blocks(seqs, rpb), dev).to(dev, non_blocking=True), self.gen.cache, None,
+                                 ws=ws, resume_after=self.layer, h_in=hin,
+                                 prefix_kv=self.pair_kv if self.tf_prefix else None)
+            xs = x[:rows].clone()
+            r0 = 0
+            for p, _ in grp:
+                n = p.resid.shape[0]
+                p.x_base = (p.resid, xs[r0:r0 + n])
+                r0 += n
+            self.stats["shift_base_pass_rows"] = self.stats.get("shift_base_pass_rows", 0) + rows
+        parts = [p.x_base[1] if p.resid.shape[0] else p.resid.new_zeros(0, self.D) for p in upairs]
+        return torch.cat(parts, 0) if len(parts) > 1 else parts[0]
+
+    @staticmethod
+    def _shift_fields(p: Pair, f: int, r0: int, kl: Optional[np.ndarray], kl_rev: Optional[np.ndarray]) -> dict:
+        """Record fields of the output shift for a cell whose teacher-forced tail starts at response index ``f`` (row
+        ``r0`` of ``kl`` / ``kl_rev``; tail row ``t`` holds the KL between the baseline's and the cell's distribution
+        over token ``t + 1``, both after the baseline's tokens ``0..t``).  ``kl_out_mean`` / ``kl_rev_out_mean`` run
+        over the positions of the cell's ``nll_edit`` -- the ``n`` response tokens, of which the first ``f + 1`` are
+        chosen before the first edit and shift by exactly 0 -- and ``kl_out_max`` over the same; ``kl_out_spike_mean``
+        over the pair's spikes ``t`` (row ``t``, the row right behind the edit; spikes before ``f`` were no-op edits:
+        0).  The sums are exactly rounded (``math.fsum``), so a cell's fields do not depend on where its rows lie in
+        the tail or on leading zero rows."""
+        import math
+
+        n = len(p.resp)
+        ntail = max(0, n - 1 - f)
+        rows = kl[r0: r0 + ntail] if kl is not None else np.zeros(0, np.float32)
+        rrev = kl_rev[r0: r0 + ntail] if kl_rev is not None else np.zeros(0, np.float32)
+        sp = [t for t in p.spikes_rel if t < n]
+        hit = [float(kl[r0 + t - f]) for t in sp if t >= f] if kl is not None else []
+        return {"kl_out_mean": math.fsum(rows.tolist()) / n if n else 0.0,
+                "kl_out_max": max([0.0] + rows.tolist()),
+                "kl_out_spike_mean": math.fsum(hit) / len(sp) if sp else 0.0,
+                "kl_rev_out_mean": math.fsum(rrev.tolist()) / n if n else 0.0}
 
     def _cell_result(self, c: Cell, p: Pair, n_gen: int, resp: List[int], probs: np.ndarray, topk_ids: List[int],
                      nll_edit: float, nll_self: float, ro=None) -> dict:

@@ -82,6 +82,9 @@ class Pair:
     # distribution that chose each generated token (index 0: the prefill's last prompt row), from the baseline's decode
     out_logp: Optional[np.ndarray] = None
     out_rank: Optional[np.ndarray] = None
+    # intervention.output_shift only: (the ``resid`` they were computed from, [n, D] final-normed rows of the unedited
+    # blocks past the hooked layer over ``resid``) -- the baseline side of the cells' KL (ReadoutMixin._shift_base)
+    x_base: Optional[tuple] = None
 
     def ro_order(self) -> List[int]:
         """Column order of ``track`` in the tracking head's id table (output readout): the secret's two forms, the

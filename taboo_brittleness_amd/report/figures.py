@@ -7,6 +7,9 @@
   (token-forcing success when measured, else leak rate), one point per setting;
 * ``fig4_interchange.png`` — interchange (donor-swap) interventions, only for sweeps that ran them: the
   target's and the donor's secret probability vs budget / rank, targeted swap vs random swap;
+* ``fig5_collateral.png`` — output shift (``intervention.output_shift``), only for sweeps run with it: the KL between
+  the baseline's and the edited next-token distribution vs budget / rank, targeted against its controls; with the
+  output readout also the specificity plane (Δ log-prob of the secret against that KL);
 * ``table_baselines.csv`` — LL-Top-k / SAE-Top-k / token forcing rows with
   Pass@10, Majority@10, Accuracy.
 """
@@ -210,6 +213,57 @@ def content_vs_output(summary: Dict, path: str) -> None:
     plt.close(fig)
 
 
+def _method_colour(method: str) -> str:
+    return "tab:red" if method.endswith("targeted") else "tab:green" if method.endswith("noise") else \
+        "tab:purple" if "swap" in method else "0.4" if method == "sae_splice" else "tab:blue"
+
+
+def collateral_curves(summary: Dict, path: str) -> None:
+    """Output shift (intervention.output_shift): ``kl_out_mean`` -- KL(baseline || edited) of the next-token
+    distribution, averaged over the teacher-forced response -- against budget m (SAE methods) and rank r (subspace
+    methods), every method the sweep ran (targeted against its random / noise / swap controls, the pure splice as a
+    level), with 95 % bootstrap intervals.  With the output readout a further panel, the specificity plane: what the
+    edit did to the secret's own log-prob (``delta_logp_out``) against what it did to the whole distribution."""
+    curves = [c for c in summary["curves"] if "kl_out_mean" in c]
+    plane = any("delta_logp_out" in c for c in curves)
+    fig, axes = plt.subplots(1, 2 + int(plane), figsize=(5.5 * (2 + int(plane)), 4.2), squeeze=False)
+    for ax, (kind, xlabel) in zip(axes[0], (("sae", "budget m"), ("proj", "rank r"))):
+        for meth in sorted({c["method"] for c in curves if c["method"].startswith(kind + "_")}):
+            xs, ys, lo, hi = _curve(curves, meth, "kl_out_mean")
+            if meth == "sae_splice":
+                ax.axhline(ys[0], color="0.4", ls="--", lw=1, label="sae_splice (nothing ablated)")
+                continue
+            ls = "o-" if meth.endswith("targeted") or meth.endswith("_swap") else "s--"
+            ax.plot(xs, ys, ls, color=_method_colour(meth), label=meth, alpha=0.9)
+            ax.fill_between(xs, lo, hi, color=_method_colour(meth), alpha=0.15)
+        ax.set_xscale("log", base=2)
+        ax.set_xlabel(xlabel)
+        ax.set_ylabel("KL(baseline || edited), nats per response token")
+        ax.set_title(f"collateral shift of the output distribution: {kind}")
+        if ax.get_legend_handles_labels()[0]:
+            ax.legend(fontsize=7)
+    if plane:
+        ax = axes[0][2]
+        for c in curves:
+            if "delta_logp_out" not in c:
+                continue
+            x, y = c["kl_out_mean"], c["delta_logp_out"]
+            ax.errorbar([x["mean"]], [y["mean"]], xerr=[[x["mean"] - x["lo"]], [x["hi"] - x["mean"]]],
+                        yerr=[[y["mean"] - y["lo"]], [y["hi"] - y["mean"]]], color=_method_colour(c["method"]),
+                        marker="o" if c["method"].startswith("sae") else "s", capsize=2, lw=0.8)
+            ax.annotate(f"{c['method'].split('_')[0]}{c['budget']}", (x["mean"], y["mean"]), fontsize=7)
+        ax.axhline(0, color="k", lw=0.5)
+        ax.set_xlabel("KL(baseline || edited) (everything)")
+        ax.set_ylabel("Δ next-token log-prob of the secret (the target)")
+        ax.set_title("specificity plane")
+    if mode_label(summary):
+        fig.suptitle(f"sae cells: {mode_label(summary)}")
+    plt.tight_layout()
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    fig.savefig(path, dpi=150)
+    plt.close(fig)
+
+
 def baselines_table(rows: Dict[str, Dict[str, float]], path: str) -> None:
     lines = ["method,pass@10,majority@10,accuracy"]
     for name, m in rows.items():
@@ -246,6 +300,10 @@ def make_report(results_dir: str, out_dir: str) -> List[str]:
             if any("delta_logp_out" in c for c in s["curves"]):    # only sweeps run with the output readout
                 p = os.path.join(out_dir, f"fig3b_content_vs_output_{tag}.png")
                 content_vs_output(s, p)
+                made.append(p)
+            if any("kl_out_mean" in c for c in s["curves"]):       # only sweeps run with the output shift
+                p = os.path.join(out_dir, f"fig5_collateral_{tag}.png")
+                collateral_curves(s, p)
                 made.append(p)
             if s.get("baselines"):
                 from .dashboards import write_latent_dashboard
