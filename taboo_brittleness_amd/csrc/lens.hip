@@ -22,6 +22,7 @@
 #include "api.h"
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 namespace {
 
@@ -132,9 +133,52 @@ __device__ __forceinline__ void stream_row(const uint4* __restrict__ p, int nv, 
   }
   for (; c < nv; c += st) f(p[c], c);
 }
-constexpr int ROW_UNR = 4;
-inline int row_unr() { return ROW_UNR; }
+constexpr int ROW_UNR = 4;   // (8 loads in flight per lane measured 2-5 % slower than 4: profiles/r3/dh5)
 
+// ---- capping policies of the running-max row pass ---------------------------------------------------------
+// stage() puts its table into LDS (block-wide, ends in a barrier where it copied), then
+// cap8 / cap1 give the capped fp32 logits of a 16-B vector / of one bf16.
+// CapRun: capped8 / capped1 with their runtime dispatch (64 KB table, emulated compute, fp32 tanh, or none).
+struct CapRun {
+  const uint16_t* ct;   // the registered table (or nullptr); after stage() its LDS copy
+  float cap;
+  int emu;
+  __device__ __forceinline__ void stage() {
+    extern __shared__ __attribute__((aligned(16))) uint16_t ctab_lds[];
+    ct = stage_ctab(ct, ctab_lds);
+  }
+  __device__ __forceinline__ void cap8(const uint4& v, float* f) const { capped8(v, f, ct, cap, emu); }
+  __device__ __forceinline__ float cap1(uint16_t b) const { return capped1(b, ct, cap, emu); }
+};
+// CapRunEmu: CapRun with emulate_bf16 a constant, as decode_head needs it (no fp32-tanh code in its kernel)
+struct CapRunEmu : CapRun {
+  __device__ __forceinline__ void cap8(const uint4& v, float* f) const { capped8(v, f, ct, cap, 1); }
+  __device__ __forceinline__ float cap1(uint16_t b) const { return capped1(b, ct, cap, 1); }
+};
+// CapCompact: the compact softcap (see CapC) on its ~1.35 KB static LDS table
+struct CapCompact {
+  CapC c;
+  const uint16_t* lt;   // set by stage()
+  __device__ __forceinline__ void stage() {
+    __shared__ __attribute__((aligned(16))) uint16_t lds[CAPC_MAX];
+    for (int i = threadIdx.x; i < c.hi - c.lo; i += blockDim.x) lds[i] = c.tab[i];
+    __syncthreads();
+    lt = lds;
+  }
+  __device__ __forceinline__ void cap8(const uint4& v, float* f) const {
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      f[2 * k] = capc1(w[k] & 0xffffu, lt, c);
+      f[2 * k + 1] = capc1(w[k] >> 16, lt, c);
+    }
+  }
+  __device__ __forceinline__ float cap1(uint16_t b) const { return capc1(b, lt, c); }
+};
+
+// ---- accumulators and their block reduction -----------------------------------------------------------------
+// What a lane carries over its share of a row -- ArgBest, OnlineLse, plain float sums, integer counts -- each with
+// merge(a, b) and shfl_xor(x, o), which is all that wave_reduce / block_reduce ask of a type.
 struct ArgBest {
   float v;
   int i;
@@ -144,42 +188,10 @@ __device__ __forceinline__ ArgBest better(ArgBest a, ArgBest b) {
   return a;
 }
 
-template <int UNR>
-__global__ void __launch_bounds__(512) argmax_rows_kernel(const uint16_t* __restrict__ logits,
-                                                          int32_t* __restrict__ out, int V, float cap,
-                                                          const uint16_t* __restrict__ tab) {
-  __shared__ float sv[8];
-  __shared__ int si[8];
-  extern __shared__ __attribute__((aligned(16))) uint16_t ctab_lds[];
-  const uint16_t* ct = stage_ctab(tab, ctab_lds);
-  const uint16_t* row = logits + (size_t)blockIdx.x * V;
-  ArgBest best{-INFINITY, 0x7fffffff};
-  const int nv = V >> 3;
-  stream_row<UNR>(reinterpret_cast<const uint4*>(row), nv, [&](const uint4& v, int c) {
-    float f[8];
-    capped8(v, f, ct, cap, 1);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) best = better(best, ArgBest{f[j], c * 8 + j});
-  });
-  for (int c = nv * 8 + threadIdx.x; c < V; c += blockDim.x) {
-    const float x = capped1(row[c], ct, cap, 1);
-    best = better(best, ArgBest{x, c});
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    ArgBest oth{__shfl_xor(best.v, o, 64), __shfl_xor(best.i, o, 64)};
-    best = better(best, oth);
-  }
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) { sv[wid] = best.v; si[wid] = best.i; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    ArgBest b{sv[0], si[0]};
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) b = better(b, ArgBest{sv[w], si[w]});
-    out[blockIdx.x] = b.i;
-  }
-}
-
+// online log-sum-exp: max m (-inf: nothing seen yet) and s = sum exp(x - m)
+struct OnlineLse {
+  float m, s;
+};
 __device__ __forceinline__ void online_add(float& m, float& s, float x) {
   if (x > m) {
     s = s * __expf(m - x) + 1.f;
@@ -195,44 +207,134 @@ __device__ __forceinline__ void online_merge(float& m, float& s, float m2, float
   else { s += s2 * __expf(m2 - m); }
 }
 
-template <int UNR>
-__global__ void __launch_bounds__(512) row_lse_kernel(const uint16_t* __restrict__ logits, float* __restrict__ lse,
-                                                      int V, float cap, int emulate_bf16,
-                                                      const uint16_t* __restrict__ tab) {
-  __shared__ float sm[8], ss[8];
+__device__ __forceinline__ ArgBest merge(ArgBest a, ArgBest b) { return better(a, b); }
+__device__ __forceinline__ OnlineLse merge(OnlineLse a, OnlineLse b) {
+  online_merge(a.m, a.s, b.m, b.s);
+  return a;
+}
+__device__ __forceinline__ float merge(float a, float b) { return a + b; }
+__device__ __forceinline__ int merge(int a, int b) { return a + b; }
+
+__device__ __forceinline__ float shfl_xor(float x, int o) { return __shfl_xor(x, o, 64); }
+__device__ __forceinline__ int shfl_xor(int x, int o) { return __shfl_xor(x, o, 64); }
+__device__ __forceinline__ ArgBest shfl_xor(ArgBest x, int o) { return {shfl_xor(x.v, o), shfl_xor(x.i, o)}; }
+__device__ __forceinline__ OnlineLse shfl_xor(OnlineLse x, int o) { return {shfl_xor(x.m, o), shfl_xor(x.s, o)}; }
+
+// An accumulator's per-wave LDS slots (8 waves at most), one array per scalar: a struct's fields are stored apart,
+// so no store or load needs a register pair (array-of-structs slots cost the track kernel an occupancy step)
+template <typename T>
+struct Slots {
+  T x[8];
+  __device__ __forceinline__ void put(int w, T a) { x[w] = a; }
+  __device__ __forceinline__ T get(int w) const { return x[w]; }
+};
+template <>
+struct Slots<ArgBest> {
+  float v[8];
+  int i[8];
+  __device__ __forceinline__ void put(int w, ArgBest a) { v[w] = a.v; i[w] = a.i; }
+  __device__ __forceinline__ ArgBest get(int w) const { return {v[w], i[w]}; }
+};
+template <>
+struct Slots<OnlineLse> {
+  float m[8], s[8];
+  __device__ __forceinline__ void put(int w, OnlineLse a) { m[w] = a.m; s[w] = a.s; }
+  __device__ __forceinline__ OnlineLse get(int w) const { return {m[w], s[w]}; }
+};
+
+
+// the wave's butterfly, xor 32 .. 1, over all accumulators side by side: every lane ends with the wave's value
+template <typename... T>
+__device__ __forceinline__ void wave_reduce(T&... x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) ((x = merge(x, shfl_xor(x, o))), ...);
+}
+
+// An accumulator and its __shared__ slots, one per wave (8 at most), for block_reduce: the butterfly, lane 0 of each
+// wave to the wave's slot, a barrier, then thread 0 folds the waves in order 0, 1, ... -- only thread 0 holds the
+// block's values afterwards.  The order is part of every float result's bits.  A block that reduces again (the next
+// row of a persistent kernel) needs a barrier of its own before it rewrites the slots.
+template <typename T>
+struct Red {
+  T& x;
+  Slots<T>& slot;
+};
+template <typename T>
+__device__ __forceinline__ Red<T> red(T& x, Slots<T>& slot) { return {x, slot}; }
+
+template <typename... T>
+__device__ __forceinline__ void block_reduce(Red<T>... r) {
+  wave_reduce(r.x...);
+  if ((threadIdx.x & 63) == 0) (r.slot.put(threadIdx.x >> 6, r.x), ...);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    ((r.x = r.slot.get(0)), ...);
+    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) ((r.x = merge(r.x, r.slot.get(w))), ...);
+  }
+}
+
+__global__ void __launch_bounds__(512) argmax_rows_kernel(const uint16_t* __restrict__ logits,
+                                                          int32_t* __restrict__ out, int V, float cap,
+                                                          const uint16_t* __restrict__ tab) {
+  __shared__ Slots<ArgBest> sb;
   extern __shared__ __attribute__((aligned(16))) uint16_t ctab_lds[];
   const uint16_t* ct = stage_ctab(tab, ctab_lds);
   const uint16_t* row = logits + (size_t)blockIdx.x * V;
-  float m = -INFINITY, s = 0.f;
+  ArgBest best{-INFINITY, 0x7fffffff};
   const int nv = V >> 3;
-  stream_row<UNR>(reinterpret_cast<const uint4*>(row), nv, [&](const uint4& v, int) {
+  stream_row<ROW_UNR>(reinterpret_cast<const uint4*>(row), nv, [&](const uint4& v, int c) {
     float f[8];
-    capped8(v, f, ct, cap, emulate_bf16);
+    capped8(v, f, ct, cap, 1);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) best = better(best, ArgBest{f[j], c * 8 + j});
+  });
+  for (int c = nv * 8 + threadIdx.x; c < V; c += blockDim.x) {
+    const float x = capped1(row[c], ct, cap, 1);
+    best = better(best, ArgBest{x, c});
+  }
+  block_reduce(red(best, sb));
+  if (threadIdx.x == 0) out[blockIdx.x] = best.i;
+}
+
+// One lane's share of a row's online log-sum-exp under capping policy ``cp``: the streamed 8-wide step (local max,
+// local exp-sum, one online_merge per vector), then the V % 8 tail column by column.  each(x, col) also sees
+// every capped logit, in the same order.
+template <typename Cap, typename Each>
+__device__ __forceinline__ OnlineLse lse_row(const uint16_t* row, int V, const Cap& cp, Each&& each) {
+  OnlineLse l{-INFINITY, 0.f};
+  const int nv = V >> 3;
+  stream_row<ROW_UNR>(reinterpret_cast<const uint4*>(row), nv, [&](const uint4& v, int c) {
+    float f[8];
+    cp.cap8(v, f);
     float lm = -INFINITY;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) lm = fmaxf(lm, f[j]);
+    for (int j = 0; j < 8; ++j) {
+      lm = fmaxf(lm, f[j]);
+      each(f[j], c * 8 + j);
+    }
     float ls = 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) ls += __expf(f[j] - lm);
-    online_merge(m, s, lm, ls);
+    online_merge(l.m, l.s, lm, ls);
   });
   for (int c = nv * 8 + threadIdx.x; c < V; c += blockDim.x) {
-    const float x = capped1(row[c], ct, cap, emulate_bf16);
-    if (m == -INFINITY) { m = x; s = 1.f; } else online_add(m, s, x);
+    const float x = cp.cap1(row[c]);
+    each(x, c);
+    if (l.m == -INFINITY) { l.m = x; l.s = 1.f; } else online_add(l.m, l.s, x);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-    online_merge(m, s, m2, s2);
-  }
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) { sm[wid] = m; ss[wid] = s; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float M = sm[0], Ssum = ss[0];
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) online_merge(M, Ssum, sm[w], ss[w]);
-    lse[blockIdx.x] = M + __logf(Ssum);
-  }
+  return l;
+}
+__device__ __forceinline__ float lse_of(OnlineLse l) { return l.m + __logf(l.s); }
+
+__global__ void __launch_bounds__(512) row_lse_kernel(const uint16_t* __restrict__ logits, float* __restrict__ lse,
+                                                      int V, float cap, int emulate_bf16,
+                                                      const uint16_t* __restrict__ tab) {
+  __shared__ Slots<OnlineLse> sl;
+  CapRun cp{tab, cap, emulate_bf16};
+  cp.stage();
+  OnlineLse l = lse_row(logits + (size_t)blockIdx.x * V, V, cp, [](float, int) {});
+  block_reduce(red(l, sl));
+  if (threadIdx.x == 0) lse[blockIdx.x] = lse_of(l);
 }
 
 // ``rowmap`` (optional): logical row r reads logits / lse row rowmap[r] (rows deduplicated upstream).
@@ -408,182 +510,57 @@ __global__ void __launch_bounds__(256) topk_rows_kernel(const float* __restrict_
   }
 }
 
-template <int UNR>
+// row_lse minus the capped target logit; a target outside [0, V) writes 0 and stages nothing
 __global__ void __launch_bounds__(512) xent_rows_kernel(const uint16_t* __restrict__ logits,
                                                         const int32_t* __restrict__ tgt, float* __restrict__ nll,
                                                         int V, float cap, int emulate_bf16,
                                                         const uint16_t* __restrict__ tab) {
-  __shared__ float sm[8], ss[8];
+  __shared__ Slots<OnlineLse> sl;
   const int r = blockIdx.x;
   const int t = tgt[r];
   if (t < 0 || t >= V) {
     if (threadIdx.x == 0) nll[r] = 0.f;
     return;
   }
-  extern __shared__ __attribute__((aligned(16))) uint16_t ctab_lds[];
-  const uint16_t* ct = stage_ctab(tab, ctab_lds);
+  CapRun cp{tab, cap, emulate_bf16};
+  cp.stage();
   const uint16_t* row = logits + (size_t)r * V;
-  float m = -INFINITY, s = 0.f;
-  const int nv = V >> 3;
-  stream_row<UNR>(reinterpret_cast<const uint4*>(row), nv, [&](const uint4& v, int) {
-    float f[8];
-    capped8(v, f, ct, cap, emulate_bf16);
-    float lm = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) lm = fmaxf(lm, f[j]);
-    float ls = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) ls += __expf(f[j] - lm);
-    online_merge(m, s, lm, ls);
-  });
-  for (int c = nv * 8 + threadIdx.x; c < V; c += blockDim.x) {
-    const float x = capped1(row[c], ct, cap, emulate_bf16);
-    if (m == -INFINITY) { m = x; s = 1.f; } else online_add(m, s, x);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-    online_merge(m, s, m2, s2);
-  }
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) { sm[wid] = m; ss[wid] = s; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float M = sm[0], Ssum = ss[0];
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) online_merge(M, Ssum, sm[w], ss[w]);
-    const float zt = capped1(row[t], ct, cap, emulate_bf16);
-    nll[r] = (M + __logf(Ssum)) - zt;
+  OnlineLse l = lse_row(row, V, cp, [](float, int) {});
+  block_reduce(red(l, sl));
+  if (threadIdx.x == 0) nll[r] = lse_of(l) - cp.cap1(row[t]);
+}
+
+// What thread 0 writes for row r of a decode_head pass: the greedy token, its NLL and, with nll_tgt, the NLL of the
+// teacher target (0 for a target outside [0, V)).  zt(t): the capped logit of column t.
+template <typename Zt>
+__device__ __forceinline__ void head_write(int r, float lse, ArgBest b, const int32_t* __restrict__ tgt,
+                                           int32_t* __restrict__ nxt, float* __restrict__ nll_self,
+                                           float* __restrict__ nll_tgt, int V, Zt&& zt) {
+  nxt[r] = b.i;
+  nll_self[r] = lse - b.v;
+  if (nll_tgt != nullptr) {
+    const int t = tgt[r];
+    nll_tgt[r] = (t >= 0 && t < V) ? lse - zt(t) : 0.f;
   }
 }
 
-template <int UNR>
+// decode_head with a running max, one block per row: every cap the fixed-offset kernel below does not take, and
+// TB_DECODE_HEAD=t / c.  CapRunEmu and CapCompact give the same capped values in the same order, so the same outputs.
+template <typename Cap>
 __global__ void __launch_bounds__(512) decode_head_kernel(const uint16_t* __restrict__ logits,
                                                           const int32_t* __restrict__ tgt, int32_t* __restrict__ nxt,
                                                           float* __restrict__ nll_self, float* __restrict__ nll_tgt,
-                                                          int V, float cap, const uint16_t* __restrict__ tab) {
-  __shared__ float sm[8], ss[8], sv[8];
-  __shared__ int si[8];
-  extern __shared__ __attribute__((aligned(16))) uint16_t ctab_lds[];
-  const uint16_t* ct = stage_ctab(tab, ctab_lds);
+                                                          int V, Cap cp) {
+  __shared__ Slots<OnlineLse> sl;
+  __shared__ Slots<ArgBest> sb;
+  cp.stage();
   const int r = blockIdx.x;
   const uint16_t* row = logits + (size_t)r * V;
-  float m = -INFINITY, s = 0.f;
   ArgBest best{-INFINITY, 0x7fffffff};
-  const int nv = V >> 3;
-  stream_row<UNR>(reinterpret_cast<const uint4*>(row), nv, [&](const uint4& v, int c) {
-    float f[8];
-    capped8(v, f, ct, cap, 1);
-    float lm = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      lm = fmaxf(lm, f[j]);
-      best = better(best, ArgBest{f[j], c * 8 + j});
-    }
-    float ls = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) ls += __expf(f[j] - lm);
-    online_merge(m, s, lm, ls);
-  });
-  for (int c = nv * 8 + threadIdx.x; c < V; c += blockDim.x) {
-    const float x = capped1(row[c], ct, cap, 1);
-    best = better(best, ArgBest{x, c});
-    if (m == -INFINITY) { m = x; s = 1.f; } else online_add(m, s, x);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-    online_merge(m, s, m2, s2);
-    ArgBest oth{__shfl_xor(best.v, o, 64), __shfl_xor(best.i, o, 64)};
-    best = better(best, oth);
-  }
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) { sm[wid] = m; ss[wid] = s; sv[wid] = best.v; si[wid] = best.i; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float M = sm[0], Ssum = ss[0];
-    ArgBest b{sv[0], si[0]};
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) {
-      online_merge(M, Ssum, sm[w], ss[w]);
-      b = better(b, ArgBest{sv[w], si[w]});
-    }
-    const float lse = M + __logf(Ssum);
-    nxt[r] = b.i;
-    nll_self[r] = lse - b.v;
-    if (nll_tgt != nullptr) {
-      const int t = tgt[r];
-      float zt = 0.f;
-      if (t >= 0 && t < V) zt = capped1(row[t], ct, cap, 1);
-      nll_tgt[r] = (t >= 0 && t < V) ? lse - zt : 0.f;
-    }
-  }
-}
-
-// decode_head on the compact softcap (see CapC): same outputs as decode_head_kernel with the full table
-template <int UNR>
-__global__ void __launch_bounds__(512) decode_head_c_kernel(const uint16_t* __restrict__ logits,
-                                                            const int32_t* __restrict__ tgt, int32_t* __restrict__ nxt,
-                                                            float* __restrict__ nll_self, float* __restrict__ nll_tgt,
-                                                            int V, CapC cc) {
-  __shared__ float sm[8], ss[8], sv[8];
-  __shared__ int si[8];
-  __shared__ __attribute__((aligned(16))) uint16_t lt[CAPC_MAX];
-  for (int i = threadIdx.x; i < cc.hi - cc.lo; i += blockDim.x) lt[i] = cc.tab[i];
-  __syncthreads();
-  const int r = blockIdx.x;
-  const uint16_t* row = logits + (size_t)r * V;
-  float m = -INFINITY, s = 0.f;
-  ArgBest best{-INFINITY, 0x7fffffff};
-  const int nv = V >> 3;
-  stream_row<UNR>(reinterpret_cast<const uint4*>(row), nv, [&](const uint4& v, int c) {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-    float f[8];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      f[2 * k] = capc1(w[k] & 0xffffu, lt, cc);
-      f[2 * k + 1] = capc1(w[k] >> 16, lt, cc);
-    }
-    float lm = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      lm = fmaxf(lm, f[j]);
-      best = better(best, ArgBest{f[j], c * 8 + j});
-    }
-    float ls = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) ls += __expf(f[j] - lm);
-    online_merge(m, s, lm, ls);
-  });
-  for (int c = nv * 8 + threadIdx.x; c < V; c += blockDim.x) {
-    const float x = capc1(row[c], lt, cc);
-    best = better(best, ArgBest{x, c});
-    if (m == -INFINITY) { m = x; s = 1.f; } else online_add(m, s, x);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-    online_merge(m, s, m2, s2);
-    ArgBest oth{__shfl_xor(best.v, o, 64), __shfl_xor(best.i, o, 64)};
-    best = better(best, oth);
-  }
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) { sm[wid] = m; ss[wid] = s; sv[wid] = best.v; si[wid] = best.i; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float M = sm[0], Ssum = ss[0];
-    ArgBest b{sv[0], si[0]};
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) {
-      online_merge(M, Ssum, sm[w], ss[w]);
-      b = better(b, ArgBest{sv[w], si[w]});
-    }
-    const float lse = M + __logf(Ssum);
-    nxt[r] = b.i;
-    nll_self[r] = lse - b.v;
-    if (nll_tgt != nullptr) {
-      const int t = tgt[r];
-      const float zt = (t >= 0 && t < V) ? capc1(row[t], lt, cc) : 0.f;
-      nll_tgt[r] = (t >= 0 && t < V) ? lse - zt : 0.f;
-    }
-  }
+  OnlineLse l = lse_row(row, V, cp, [&](float x, int c) { best = better(best, ArgBest{x, c}); });
+  block_reduce(red(l, sl), red(best, sb));
+  if (threadIdx.x == 0)
+    head_write(r, lse_of(l), best, tgt, nxt, nll_self, nll_tgt, V, [&](int t) { return cp.cap1(row[t]); });
 }
 
 // decode_head for 0 < cap <= DH_FIXED_CAP, the default: the same outputs as decode_head_kernel (argmax bit-exact,
@@ -629,6 +606,49 @@ __device__ __forceinline__ float fmax_raw(float a, float b) {
 typedef float f2 __attribute__((ext_vector_type(2)));
 constexpr f2 LOG2E2 = {1.4426950408889634f, 1.4426950408889634f};
 
+// One lane's share of a row on the fixed-offset path (decode_head_f_kernel and decode_head_track_kernel run these
+// statements, so their nxt / nll_self / nll_tgt have the same bits): the exp-sum as two packed halves and the best
+// 8-logit chunk; finish() turns them into the lane's sum and ArgBest.
+struct FixedAcc {
+  f2 s2 = {0.f, 0.f};
+  float bv = -INFINITY;
+  int bc = -1;
+
+  // the 8 logits of vector c; their capped values stay in f for the caller
+  __device__ __forceinline__ void chunk(const uint4& v, int c, const uint16_t* ct, float* f) {
+    capped8_tab(v, f, ct);
+    const float cm = max3_raw(max3_raw(f[0], f[1], f[2]), max3_raw(f[3], f[4], f[5]), fmax_raw(f[6], f[7]));
+#pragma unroll
+    for (int j = 0; j < 8; j += 2) {   // packed scale / add (v_pk_mul_f32, v_pk_add_f32), exp2 per lane
+      const f2 y = f2{f[j], f[j + 1]} * LOG2E2;
+      s2 += f2{__builtin_amdgcn_exp2f(y.x), __builtin_amdgcn_exp2f(y.y)};
+    }
+    if (cm > bv) { bv = cm; bc = c; }
+  }
+
+  // after the stream: the index inside the winning chunk (re-read; the first of the maxima), then the V % 8 tail
+  // column by column; tail(x) also sees each tail column's capped logit
+  template <typename Tail>
+  __device__ __forceinline__ void finish(const uint16_t* row, int V, const uint16_t* ct, float& s, ArgBest& best,
+                                         Tail&& tail) const {
+    s = s2.x + s2.y;
+    best = ArgBest{bv, 0x7fffffff};
+    if (bc >= 0) {
+      float f[8];
+      capped8(reinterpret_cast<const uint4*>(row)[bc], f, ct, 0.f, 1);
+#pragma unroll
+      for (int j = 7; j >= 0; --j)
+        if (f[j] == bv) best.i = bc * 8 + j;
+    }
+    for (int c = (V >> 3) * 8 + threadIdx.x; c < V; c += blockDim.x) {
+      const float x = capped1(row[c], ct, 0.f, 1);
+      s += __expf(x);
+      best = better(best, ArgBest{x, c});
+      tail(x);
+    }
+  }
+};
+
 // stats != nullptr (vocab-parallel TP head, models/gemma2.py): instead of the token / NLLs, per row the float4
 // {log-sum-exp, best capped logit, its global vocab id (local + off), the capped logit of the teacher target
 // tgt - off if it falls in this rank's [0, V) slice, else -inf}, merged over the ranks by vp_head_merge (vp.hip)
@@ -638,79 +658,39 @@ __global__ void __launch_bounds__(512) decode_head_f_kernel(const uint16_t* __re
                                                             float* __restrict__ nll_self, float* __restrict__ nll_tgt,
                                                             int R, int V, const uint16_t* __restrict__ tab,
                                                             float4* __restrict__ stats, int off) {
-  __shared__ float ss[8], sv[8];
-  __shared__ int si[8];
+  __shared__ Slots<float> ss;
+  __shared__ Slots<ArgBest> sb;
   extern __shared__ __attribute__((aligned(16))) uint16_t ctab_lds[];
   const uint16_t* ct = stage_ctab(tab, ctab_lds);
-  const int nv = V >> 3;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   for (int r = blockIdx.x; r < R; r += gridDim.x) {
     const uint16_t* row = logits + (size_t)r * V;
-    float s = 0.f, bv = -INFINITY;
-    int bc = -1;
-    f2 s2 = {0.f, 0.f};
-    stream_row<UNR>(reinterpret_cast<const uint4*>(row), nv, [&](const uint4& v, int c) {
+    FixedAcc a;
+    stream_row<UNR>(reinterpret_cast<const uint4*>(row), V >> 3, [&](const uint4& v, int c) {
       float f[8];
-      capped8_tab(v, f, ct);
-      const float cm = max3_raw(max3_raw(f[0], f[1], f[2]), max3_raw(f[3], f[4], f[5]), fmax_raw(f[6], f[7]));
-#pragma unroll
-      for (int j = 0; j < 8; j += 2) {   // packed scale / add (v_pk_mul_f32, v_pk_add_f32), exp2 per lane
-        const f2 y = f2{f[j], f[j + 1]} * LOG2E2;
-        s2 += f2{__builtin_amdgcn_exp2f(y.x), __builtin_amdgcn_exp2f(y.y)};
-      }
-      if (cm > bv) { bv = cm; bc = c; }
+      a.chunk(v, c, ct, f);
     });
-    s = s2.x + s2.y;
-    ArgBest best{bv, 0x7fffffff};
-    if (bc >= 0) {
-      float f[8];
-      capped8(reinterpret_cast<const uint4*>(row)[bc], f, ct, 0.f, 1);
-#pragma unroll
-      for (int j = 7; j >= 0; --j)
-        if (f[j] == bv) best.i = bc * 8 + j;
-    }
-    for (int c = nv * 8 + threadIdx.x; c < V; c += blockDim.x) {
-      const float x = capped1(row[c], ct, 0.f, 1);
-      s += __expf(x);
-      best = better(best, ArgBest{x, c});
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      s += __shfl_xor(s, o, 64);
-      ArgBest oth{__shfl_xor(best.v, o, 64), __shfl_xor(best.i, o, 64)};
-      best = better(best, oth);
-    }
-    if (lane == 0) { ss[wid] = s; sv[wid] = best.v; si[wid] = best.i; }
-    __syncthreads();
+    float s;
+    ArgBest best;
+    a.finish(row, V, ct, s, best, [](float) {});
+    block_reduce(red(s, ss), red(best, sb));
     if (threadIdx.x == 0) {
-      float Ssum = ss[0];
-      ArgBest b{sv[0], si[0]};
-      for (int w = 1; w < (int)(blockDim.x >> 6); ++w) {
-        Ssum += ss[w];
-        b = better(b, ArgBest{sv[w], si[w]});
-      }
-      const float lse = __logf(Ssum);
+      const float lse = __logf(s);
       if (stats != nullptr) {
         const int t = tgt != nullptr ? tgt[r] - off : -1;
         const float tl = (tgt != nullptr && tgt[r] >= 0 && t >= 0 && t < V) ? capped1(row[t], ct, 0.f, 1) : -INFINITY;
-        stats[r] = make_float4(lse, b.v, (float)(b.i + off), tl);   // vocab ids < 2^24: exact in fp32
+        stats[r] = make_float4(lse, best.v, (float)(best.i + off), tl);   // vocab ids < 2^24: exact in fp32
       } else {
-        nxt[r] = b.i;
-        nll_self[r] = lse - b.v;
-        if (nll_tgt != nullptr) {
-          const int t = tgt[r];
-          nll_tgt[r] = (t >= 0 && t < V) ? lse - capped1(row[t], ct, 0.f, 1) : 0.f;
-        }
+        head_write(r, lse, best, tgt, nxt, nll_self, nll_tgt, V, [&](int t) { return capped1(row[t], ct, 0.f, 1); });
       }
     }
-    __syncthreads();   // ss / sv / si are rewritten by the next row
+    __syncthreads();   // the slots are rewritten by the next row
   }
 }
 
 // decode_head_f_kernel (plain mode) plus the output-side readout of T <= DH_TRACK_MAX tracked vocab ids per row:
 // logp = capped logit - lse, and for the first n_rank <= NR columns the rank #{v : c(z[v]) > c(z[id])} (strict, so a
 // saturated tie group shares rank 0).  The ranked columns' logits are read before the stream (broadcast loads).  The
-// exp-sum and the chunk argmax are the plain kernel's statement for statement, so nxt / nll_self / nll_tgt keep its
+// exp-sum and the chunk argmax are the plain kernel's (FixedAcc, head_write), so nxt / nll_self / nll_tgt keep its
 // bits; the compares ride along on the same capped floats.  Counting costs one VALU op per logit and ranked column:
 // v_cmp_gt_f32 against the wave-uniform threshold writes the wave's lane mask to an SGPR pair, and the population
 // count and the add run on the scalar unit beside the vector stream (no packed f32 compare exists, and packed 16-bit
@@ -729,19 +709,18 @@ struct HeadTrack {
   int T, n_rank, W;
 };
 
-template <int UNR, int NR>
+template <int NR>
 __global__ void __launch_bounds__(512) decode_head_track_kernel(const uint16_t* __restrict__ logits,
                                                                 const int32_t* __restrict__ tgt,
                                                                 int32_t* __restrict__ nxt, float* __restrict__ nll_self,
                                                                 float* __restrict__ nll_tgt, int R, int V,
                                                                 const uint16_t* __restrict__ tab, HeadTrack tk) {
-  __shared__ float ss[8], sv[8];
-  __shared__ int si[8];
+  __shared__ Slots<float> ss;
+  __shared__ Slots<ArgBest> sb;
   __shared__ int sc[8][NR > 0 ? NR : 1];
   extern __shared__ __attribute__((aligned(16))) uint16_t ctab_lds[];
   const uint16_t* ct = stage_ctab(tab, ctab_lds);
   const int nv = V >> 3;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   for (int r = blockIdx.x; r < R; r += gridDim.x) {
     const uint16_t* row = logits + (size_t)r * V;
     // thresholds of the ranked columns (+inf: empty or unranked, nothing counts); only these stay live over the stream
@@ -755,25 +734,13 @@ __global__ void __launch_bounds__(512) decode_head_track_kernel(const uint16_t* 
       wcnt[k] = 0;
       lcnt[k] = 0;
     }
-    float s = 0.f, bv = -INFINITY;
-    int bc = -1;
-    f2 s2 = {0.f, 0.f};
-    // the plain kernel's per-chunk statements; f stays for the counting
-    auto chunk = [&](const uint4& v, int c, float* f) {
-      capped8_tab(v, f, ct);
-      const float cm = max3_raw(max3_raw(f[0], f[1], f[2]), max3_raw(f[3], f[4], f[5]), fmax_raw(f[6], f[7]));
-#pragma unroll
-      for (int j = 0; j < 8; j += 2) {
-        const f2 y = f2{f[j], f[j + 1]} * LOG2E2;
-        s2 += f2{__builtin_amdgcn_exp2f(y.x), __builtin_amdgcn_exp2f(y.y)};
-      }
-      if (cm > bv) { bv = cm; bc = c; }
-    };
+    FixedAcc a;
     // stream_row's order per lane (c = tid, tid + stride, ...: the same reductions), split by the wave instead of by
     // the lane: UNR-deep trips run while the wave's LAST lane still has all UNR chunks, so every lane is active in
     // them and the ballot counts the whole wave; what is left (up to UNR chunks per lane, ragged over the lanes) is
     // counted per lane
     {
+      constexpr int UNR = ROW_UNR;
       const uint4* p = reinterpret_cast<const uint4*>(row);
       const int st = blockDim.x;
       int c = threadIdx.x;
@@ -785,7 +752,7 @@ __global__ void __launch_bounds__(512) decode_head_track_kernel(const uint16_t* 
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
           float f[8];
-          chunk(v[u], c + u * st, f);
+          a.chunk(v[u], c + u * st, ct, f);
 #pragma unroll
           for (int k = 0; k < NR; ++k) {
 #pragma unroll
@@ -796,7 +763,7 @@ __global__ void __launch_bounds__(512) decode_head_track_kernel(const uint16_t* 
       }
       for (; c < nv; c += st) {
         float f[8];
-        chunk(p[c], c, f);
+        a.chunk(p[c], c, ct, f);
 #pragma unroll
         for (int k = 0; k < NR; ++k) {
 #pragma unroll
@@ -804,50 +771,23 @@ __global__ void __launch_bounds__(512) decode_head_track_kernel(const uint16_t* 
         }
       }
     }
-    s = s2.x + s2.y;
-    ArgBest best{bv, 0x7fffffff};
-    if (bc >= 0) {
-      float f[8];
-      capped8(reinterpret_cast<const uint4*>(row)[bc], f, ct, 0.f, 1);
-#pragma unroll
-      for (int j = 7; j >= 0; --j)
-        if (f[j] == bv) best.i = bc * 8 + j;
-    }
-    for (int c = nv * 8 + threadIdx.x; c < V; c += blockDim.x) {
-      const float x = capped1(row[c], ct, 0.f, 1);
-      s += __expf(x);
-      best = better(best, ArgBest{x, c});
+    float s;
+    ArgBest best;
+    a.finish(row, V, ct, s, best, [&](float x) {
 #pragma unroll
       for (int k = 0; k < NR; ++k) lcnt[k] += x > thr[k] ? 1 : 0;
-    }
+    });
+    // a wave's count goes to its own slot: the waves are added up only for the columns that get a rank (below)
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      s += __shfl_xor(s, o, 64);
-      ArgBest oth{__shfl_xor(best.v, o, 64), __shfl_xor(best.i, o, 64)};
-      best = better(best, oth);
+    for (int k = 0; k < NR; ++k) wave_reduce(lcnt[k]);
+    if ((threadIdx.x & 63) == 0) {
 #pragma unroll
-      for (int k = 0; k < NR; ++k) lcnt[k] += __shfl_xor(lcnt[k], o, 64);
+      for (int k = 0; k < NR; ++k) sc[threadIdx.x >> 6][k] = wcnt[k] + lcnt[k];
     }
-    if (lane == 0) {
-      ss[wid] = s; sv[wid] = best.v; si[wid] = best.i;
-#pragma unroll
-      for (int k = 0; k < NR; ++k) sc[wid][k] = wcnt[k] + lcnt[k];
-    }
-    __syncthreads();
+    block_reduce(red(s, ss), red(best, sb));   // its barrier publishes sc as well
     if (threadIdx.x == 0) {
-      float Ssum = ss[0];
-      ArgBest b{sv[0], si[0]};
-      for (int w = 1; w < (int)(blockDim.x >> 6); ++w) {
-        Ssum += ss[w];
-        b = better(b, ArgBest{sv[w], si[w]});
-      }
-      const float lse = __logf(Ssum);
-      nxt[r] = b.i;
-      nll_self[r] = lse - b.v;
-      if (nll_tgt != nullptr) {
-        const int t = tgt[r];
-        nll_tgt[r] = (t >= 0 && t < V) ? lse - capped1(row[t], ct, 0.f, 1) : 0.f;
-      }
+      const float lse = __logf(s);
+      head_write(r, lse, best, tgt, nxt, nll_self, nll_tgt, V, [&](int t) { return capped1(row[t], ct, 0.f, 1); });
       size_t o = (size_t)r;
       if (tk.col != nullptr) o = o * tk.W + (size_t)min(max(tk.col[r], (int64_t)0), (int64_t)(tk.W - 1));
       o *= tk.T;
@@ -863,7 +803,7 @@ __global__ void __launch_bounds__(512) decode_head_track_kernel(const uint16_t* 
         tk.rank[o + k] = rk;
       }
     }
-    __syncthreads();   // ss / sv / si / sc are rewritten by the next row
+    __syncthreads();   // the slots and sc are rewritten by the next row
   }
 }
 
@@ -890,11 +830,10 @@ __global__ void __launch_bounds__(512) head_shift_kernel(const uint16_t* __restr
                                                          const int32_t* __restrict__ rowmap, float* __restrict__ kl,
                                                          float* __restrict__ kl_rev, int R, int Rb, int V,
                                                          const uint16_t* __restrict__ tab) {
-  __shared__ float sh[4][8];
+  __shared__ Slots<float> sh[4];
   extern __shared__ __attribute__((aligned(16))) uint16_t ctab_lds[];
   const uint16_t* ct = stage_ctab(tab, ctab_lds);
   const int nv = V >> 3;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   for (int r = blockIdx.x; r < R; r += gridDim.x) {
     const int b = rowmap[r];
     if (b < 0 || b >= Rb) {   // block-uniform
@@ -944,26 +883,11 @@ __global__ void __launch_bounds__(512) head_shift_kernel(const uint16_t* __restr
       a += ep * d;
       bb -= eq * d;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      sp += __shfl_xor(sp, o, 64);
-      sq += __shfl_xor(sq, o, 64);
-      a += __shfl_xor(a, o, 64);
-      bb += __shfl_xor(bb, o, 64);
-    }
-    if (lane == 0) { sh[0][wid] = sp; sh[1][wid] = sq; sh[2][wid] = a; sh[3][wid] = bb; }
-    __syncthreads();
+    block_reduce(red(sp, sh[0]), red(sq, sh[1]), red(a, sh[2]), red(bb, sh[3]));
     if (threadIdx.x == 0) {
-      float Sp = sh[0][0], Sq = sh[1][0], A = sh[2][0], B = sh[3][0];
-      for (int w = 1; w < (int)(blockDim.x >> 6); ++w) {
-        Sp += sh[0][w];
-        Sq += sh[1][w];
-        A += sh[2][w];
-        B += sh[3][w];
-      }
-      const float dl = __logf(Sp) - __logf(Sq);
-      kl[r] = A / Sp - dl;
-      kl_rev[r] = B / Sq + dl;
+      const float dl = __logf(sp) - __logf(sq);
+      kl[r] = a / sp - dl;
+      kl_rev[r] = bb / sq + dl;
     }
     __syncthreads();   // sh is rewritten by the next row
   }
@@ -977,79 +901,99 @@ __global__ void softcap_c_kernel(const uint16_t* __restrict__ x, float* __restri
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) y[i] = capc1(x[i], lt, cc);
 }
 
-struct CapCEntry {
-  int dev;
-  uint32_t capbits;
-  CapC c;
-};
-CapCEntry g_capc[16];
-int g_ncapc = 0;
+// what the host registered per (device, cap bits): the 64 KB softcap tables and the compact softcaps
+template <typename P>
+struct CapRegistry {
+  struct Entry {
+    int dev;
+    uint32_t capbits;
+    P p;
+  };
+  Entry e[16];
+  int n = 0;
 
-const CapC* find_capc(float cap) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const uint32_t cb = __builtin_bit_cast(uint32_t, cap);
-  for (int i = 0; i < g_ncapc; ++i)
-    if (g_capc[i].dev == dev && g_capc[i].capbits == cb) return &g_capc[i].c;
-  return nullptr;
-}
-
-// softcap tables registered from the host, keyed by (device, cap bits)
-struct CapTab {
-  int dev;
-  uint32_t capbits;
-  const uint16_t* ptr;
+  // the entry of ``cap`` on the current device; with ``add`` a new one is made if there is room.  nullptr: none
+  P* find(float cap, bool add = false) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const uint32_t cb = __builtin_bit_cast(uint32_t, cap);
+    for (int i = 0; i < n; ++i)
+      if (e[i].dev == dev && e[i].capbits == cb) return &e[i].p;
+    if (!add || n >= 16) return nullptr;
+    e[n] = Entry{dev, cb, P{}};
+    return &e[n++].p;
+  }
 };
-CapTab g_tabs[16];
-int g_ntabs = 0;
+CapRegistry<const uint16_t*> g_tabs;
+CapRegistry<CapC> g_capc;
 
 const uint16_t* find_tab(float cap, int emulate) {
   if (!(cap > 0.f) || !emulate) return nullptr;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const uint32_t cb = __builtin_bit_cast(uint32_t, cap);
-  for (int i = 0; i < g_ntabs; ++i)
-    if (g_tabs[i].dev == dev && g_tabs[i].capbits == cb) return g_tabs[i].ptr;
-  return nullptr;
+  const uint16_t* const* t = g_tabs.find(cap);
+  return t != nullptr ? *t : nullptr;
 }
 
-size_t tab_lds(const void* kernel, const uint16_t* tab, bool& attr_done) {
-  if (tab == nullptr) return 0;
-  if (!attr_done) {   // > 64 KB of LDS needs the opt-in; first call is never inside a graph capture
-    (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CTAB_N * 2 + 256);
-    attr_done = true;
+int cu_count() {
+  static const int ncu = [] {
+    int dev = 0, n = 0;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+    return n > 0 ? n : 256;
+  }();
+  return ncu;
+}
+
+// TB_DECODE_HEAD, read once per process: "t" the per-row 64 KB-table kernel, "c" the compact-softcap kernel (A/B;
+// both keep a running max), default "f": the fixed-offset kernels where the cap allows them
+char dh_mode() {
+  static const char mode = [] {
+    const char* e = getenv("TB_DECODE_HEAD");
+    return e != nullptr && (e[0] == 't' || e[0] == 'c') ? e[0] : 'f';
+  }();
+  return mode;
+}
+
+// Whether tb_decode_head runs the fixed-offset kernel at this cap, as the return code of the readouts that exist
+// only there: 0 yes (*tab: its table), 1 no registered table or a cap outside (0, DH_FIXED_CAP], 2 TB_DECODE_HEAD
+// selects the t / c kernel.  *tab is the registered table (or nullptr) in every case.
+int fixed_path(float cap, const uint16_t** tab) {
+  *tab = find_tab(cap, 1);
+  if (*tab == nullptr || !(cap <= DH_FIXED_CAP)) return 1;
+  return dh_mode() == 'f' ? 0 : 2;
+}
+
+// Launches one of the 512-thread row kernels, with the dynamic LDS of the 64 KB table where there is one: > 64 KB of
+// LDS needs the opt-in, once per kernel (first call is never inside a graph capture).
+template <auto Kern, typename... A>
+void launch_rows(int grid, const uint16_t* tab, hipStream_t st, A... args) {
+  size_t lds = 0;
+  if (tab != nullptr) {
+    static const hipError_t opted = hipFuncSetAttribute(reinterpret_cast<const void*>(Kern),
+                                                        hipFuncAttributeMaxDynamicSharedMemorySize, CTAB_N * 2 + 256);
+    (void)opted;
+    lds = CTAB_N * 2;
   }
-  return CTAB_N * 2;
+  hipLaunchKernelGGL(Kern, dim3(grid), dim3(512), lds, st, args...);
 }
 
 }  // namespace
 
 void tb_register_softcap_table(float cap, const uint16_t* tab) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const uint32_t cb = __builtin_bit_cast(uint32_t, cap);
-  for (int i = 0; i < g_ntabs; ++i)
-    if (g_tabs[i].dev == dev && g_tabs[i].capbits == cb) { g_tabs[i].ptr = tab; return; }
-  if (g_ntabs < 16) g_tabs[g_ntabs++] = CapTab{dev, cb, tab};
+  if (const uint16_t** t = g_tabs.find(cap, true)) *t = tab;
 }
 
 const uint16_t* tb_find_softcap_table(float cap) { return find_tab(cap, 1); }
 
 bool tb_register_softcap_compact(float cap, const uint16_t* tab, int lo, int hi, float sat) {
   if (hi < lo || hi - lo > CAPC_MAX || !(cap > 0.f)) return false;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const uint32_t cb = __builtin_bit_cast(uint32_t, cap);
-  const CapC c{tab, lo, hi, sat, 1.0f / cap, cap};
-  for (int i = 0; i < g_ncapc; ++i)
-    if (g_capc[i].dev == dev && g_capc[i].capbits == cb) { g_capc[i].c = c; return true; }
-  if (g_ncapc >= 16) return false;
-  g_capc[g_ncapc++] = CapCEntry{dev, cb, c};
+  CapC* c = g_capc.find(cap, true);
+  if (c == nullptr) return false;
+  *c = CapC{tab, lo, hi, sat, 1.0f / cap, cap};
   return true;
 }
 
 bool tb_softcap_compact_params(float cap, const uint16_t** tab, int* lo, int* hi, float* sat) {
-  const CapC* c = find_capc(cap);
+  const CapC* c = g_capc.find(cap);
   if (c == nullptr) return false;
   *tab = c->tab;
   *lo = c->lo;
@@ -1059,7 +1003,7 @@ bool tb_softcap_compact_params(float cap, const uint16_t** tab, int* lo, int* hi
 }
 
 bool tb_softcap_compact(const uint16_t* x, float* y, int n, float cap, hipStream_t st) {
-  const CapC* c = find_capc(cap);
+  const CapC* c = g_capc.find(cap);
   if (c == nullptr || n <= 0) return c != nullptr;
   hipLaunchKernelGGL(softcap_c_kernel, dim3(std::min((n + 255) / 256, 4096)), dim3(256), 0, st, x, y, n, *c);
   return true;
@@ -1067,66 +1011,28 @@ bool tb_softcap_compact(const uint16_t* x, float* y, int n, float cap, hipStream
 
 bool tb_decode_head_stats(const uint16_t* logits, const int32_t* tgt, int off, float* stats, int R, int V, float cap,
                           hipStream_t st) {
-  const uint16_t* tab = find_tab(cap, 1);
-  if (tab == nullptr || !(cap <= DH_FIXED_CAP)) return false;
+  const uint16_t* tab;
+  if (fixed_path(cap, &tab) == 1) return false;   // runs under TB_DECODE_HEAD=t / c as well
   if (R <= 0) return true;
-  static bool attr = false;
-  static const int ncu = [] {
-    int dev = 0, n = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n > 0 ? n : 256;
-  }();
-  hipLaunchKernelGGL(decode_head_f_kernel<1>, dim3(std::min(R, 2 * ncu)), dim3(512),
-                     tab_lds(reinterpret_cast<const void*>(&decode_head_f_kernel<1>), tab, attr), st, logits, tgt,
-                     nullptr, nullptr, nullptr, R, V, tab, reinterpret_cast<float4*>(stats), off);
+  // UNR = 1: nobody has measured the stats pass at ROW_UNR
+  launch_rows<decode_head_f_kernel<1>>(std::min(R, 2 * cu_count()), tab, st, logits, tgt, nullptr, nullptr, nullptr, R,
+                                       V, tab, reinterpret_cast<float4*>(stats), off);
   return true;
 }
 
 void tb_decode_head(const uint16_t* logits, const int32_t* tgt, int32_t* nxt, float* nll_self, float* nll_tgt, int R,
                     int V, float cap, hipStream_t st) {
   if (R <= 0) return;
-  // TB_DECODE_HEAD: "t" the per-row 64 KB-table kernel, "c" the compact-softcap kernel (A/B; both keep a running
-  // max), default "f": decode_head_f_kernel where the cap allows it
-  static const char mode = [] {
-    const char* e = getenv("TB_DECODE_HEAD");
-    return e != nullptr && (e[0] == 't' || e[0] == 'c') ? e[0] : 'f';
-  }();
-  const uint16_t* tab = find_tab(cap, 1);
-  if (mode == 'f' && tab != nullptr && cap <= DH_FIXED_CAP) {
-    static bool attr = false, attr1 = false;
-    static const int ncu = [] {
-      int dev = 0, n = 0;
-      (void)hipGetDevice(&dev);
-      (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-      return n > 0 ? n : 256;
-    }();
-    const int grid = std::min(R, 2 * ncu);
-    if (row_unr() == 1)   // (8 loads in flight per lane measured 2-5 % slower than 4: profiles/r3/dh5)
-      hipLaunchKernelGGL(decode_head_f_kernel<1>, dim3(grid), dim3(512),
-                         tab_lds(reinterpret_cast<const void*>(&decode_head_f_kernel<1>), tab, attr1), st, logits, tgt,
-                         nxt, nll_self, nll_tgt, R, V, tab, nullptr, 0);
-    else
-      hipLaunchKernelGGL(decode_head_f_kernel<ROW_UNR>, dim3(grid), dim3(512),
-                         tab_lds(reinterpret_cast<const void*>(&decode_head_f_kernel<ROW_UNR>), tab, attr), st, logits,
-                         tgt, nxt, nll_self, nll_tgt, R, V, tab, nullptr, 0);
-    return;
-  }
-  if (const CapC* cc = find_capc(cap); cc != nullptr && mode != 't') {
-    if (row_unr() == 1)
-      hipLaunchKernelGGL(decode_head_c_kernel<1>, dim3(R), dim3(512), 0, st, logits, tgt, nxt, nll_self, nll_tgt, V, *cc);
-    else
-      hipLaunchKernelGGL(decode_head_c_kernel<ROW_UNR>, dim3(R), dim3(512), 0, st, logits, tgt, nxt, nll_self, nll_tgt, V,
-                         *cc);
-    return;
-  }
-  static bool attr_decode_head_kernel = false, attr_decode_head_kernel1 = false;
-  if (row_unr() == 1)
-    hipLaunchKernelGGL(decode_head_kernel<1>, dim3(R), dim3(512), tab_lds(reinterpret_cast<const void*>(&decode_head_kernel<1>), tab, attr_decode_head_kernel1), st, logits, tgt, nxt,
-                     nll_self, nll_tgt, V, cap, tab);
+  const uint16_t* tab;
+  if (fixed_path(cap, &tab) == 0)
+    launch_rows<decode_head_f_kernel<ROW_UNR>>(std::min(R, 2 * cu_count()), tab, st, logits, tgt, nxt, nll_self,
+                                               nll_tgt, R, V, tab, nullptr, 0);
+  else if (const CapC* cc = g_capc.find(cap); cc != nullptr && dh_mode() != 't')
+    launch_rows<decode_head_kernel<CapCompact>>(R, nullptr, st, logits, tgt, nxt, nll_self, nll_tgt, V,
+                                                CapCompact{*cc, nullptr});
   else
-    hipLaunchKernelGGL(decode_head_kernel<ROW_UNR>, dim3(R), dim3(512), tab_lds(reinterpret_cast<const void*>(&decode_head_kernel<ROW_UNR>), tab, attr_decode_head_kernel), st, logits, tgt, nxt,
-                     nll_self, nll_tgt, V, cap, tab);
+    launch_rows<decode_head_kernel<CapRunEmu>>(R, tab, st, logits, tgt, nxt, nll_self, nll_tgt, V,
+                                               CapRunEmu{{tab, cap, 1}});
 }
 
 // decode_head + tracked-id readout (decode_head_track_kernel).  Only where tb_decode_head runs the f kernel: returns 1
@@ -1136,29 +1042,19 @@ int tb_decode_head_track(const uint16_t* logits, const int32_t* tgt, int32_t* nx
                          const int32_t* track, int T, int n_rank, float* logp, int32_t* rank, const int64_t* col, int W,
                          int R, int V, float cap, hipStream_t st) {
   if (T < 1 || T > DH_TRACK_MAX || n_rank < 0 || n_rank > T || (col != nullptr && W < 1)) return 3;
-  const uint16_t* tab = find_tab(cap, 1);
-  if (tab == nullptr || !(cap <= DH_FIXED_CAP)) return 1;
-  const char* e = getenv("TB_DECODE_HEAD");
-  if (e != nullptr && (e[0] == 't' || e[0] == 'c')) return 2;
+  const uint16_t* tab;
+  if (const int rc = fixed_path(cap, &tab); rc != 0) return rc;
   if (R <= 0) return 0;
-  static const int ncu = [] {
-    int dev = 0, n = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n > 0 ? n : 256;
-  }();
-  const dim3 grid(std::min(R, 2 * ncu));
+  const int grid = std::min(R, 2 * cu_count());
   const HeadTrack tk{track, logp, rank, col, T, n_rank, W};
-  static bool attr0 = false, attr2 = false, attr4 = false, attr8 = false;
-#define TB_DH_TRACK(NR, ATTR)                                                                                         \
-  hipLaunchKernelGGL((decode_head_track_kernel<ROW_UNR, NR>), grid, dim3(512),                                        \
-                     tab_lds(reinterpret_cast<const void*>(&decode_head_track_kernel<ROW_UNR, NR>), tab, ATTR), st,    \
-                     logits, tgt, nxt, nll_self, nll_tgt, R, V, tab, tk)
-  if (n_rank == 0) TB_DH_TRACK(0, attr0);
-  else if (n_rank <= 2) TB_DH_TRACK(2, attr2);
-  else if (n_rank <= 4) TB_DH_TRACK(4, attr4);
-  else TB_DH_TRACK(8, attr8);
-#undef TB_DH_TRACK
+  auto go = [&](auto nr) {
+    launch_rows<decode_head_track_kernel<decltype(nr)::value>>(grid, tab, st, logits, tgt, nxt, nll_self, nll_tgt, R, V,
+                                                               tab, tk);
+  };
+  if (n_rank == 0) go(std::integral_constant<int, 0>{});
+  else if (n_rank <= 2) go(std::integral_constant<int, 2>{});
+  else if (n_rank <= 4) go(std::integral_constant<int, 4>{});
+  else go(std::integral_constant<int, 8>{});
   return 0;
 }
 
@@ -1168,46 +1064,24 @@ int tb_decode_head_track(const uint16_t* logits, const int32_t* tgt, int32_t* nx
 int tb_head_shift(const uint16_t* logits, const uint16_t* base, const int32_t* rowmap, float* kl, float* kl_rev, int R,
                   int Rb, int V, float cap, hipStream_t st) {
   if (V < 1 || Rb < 0) return 3;
-  const uint16_t* tab = find_tab(cap, 1);
-  if (tab == nullptr || !(cap <= DH_FIXED_CAP)) return 1;
-  const char* e = getenv("TB_DECODE_HEAD");
-  if (e != nullptr && (e[0] == 't' || e[0] == 'c')) return 2;
+  const uint16_t* tab;
+  if (const int rc = fixed_path(cap, &tab); rc != 0) return rc;
   if (R <= 0) return 0;
-  static const int ncu = [] {
-    int dev = 0, n = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n > 0 ? n : 256;
-  }();
-  static bool attr = false;
-  hipLaunchKernelGGL(head_shift_kernel<2>, dim3(std::min(R, 2 * ncu)), dim3(512),
-                     tab_lds(reinterpret_cast<const void*>(&head_shift_kernel<2>), tab, attr), st, logits, base, rowmap,
-                     kl, kl_rev, R, Rb, V, tab);
+  launch_rows<head_shift_kernel<2>>(std::min(R, 2 * cu_count()), tab, st, logits, base, rowmap, kl, kl_rev, R, Rb, V,
+                                    tab);
   return 0;
 }
 
 void tb_argmax_rows(const uint16_t* logits, int32_t* out, int R, int V, float cap, hipStream_t st) {
   if (R <= 0) return;
   const uint16_t* tab = find_tab(cap, 1);
-  static bool attr_argmax_rows_kernel = false, attr_argmax_rows_kernel1 = false;
-  if (row_unr() == 1)
-    hipLaunchKernelGGL(argmax_rows_kernel<1>, dim3(R), dim3(512), tab_lds(reinterpret_cast<const void*>(&argmax_rows_kernel<1>), tab, attr_argmax_rows_kernel1), st, logits, out, V, cap,
-                     tab);
-  else
-    hipLaunchKernelGGL(argmax_rows_kernel<ROW_UNR>, dim3(R), dim3(512), tab_lds(reinterpret_cast<const void*>(&argmax_rows_kernel<ROW_UNR>), tab, attr_argmax_rows_kernel), st, logits, out, V, cap,
-                     tab);
+  launch_rows<argmax_rows_kernel>(R, tab, st, logits, out, V, cap, tab);
 }
 
 void tb_row_lse(const uint16_t* logits, float* lse, int R, int V, float cap, int emulate_bf16, hipStream_t st) {
   if (R <= 0) return;
   const uint16_t* tab = find_tab(cap, emulate_bf16);
-  static bool attr_row_lse_kernel = false, attr_row_lse_kernel1 = false;
-  if (row_unr() == 1)
-    hipLaunchKernelGGL(row_lse_kernel<1>, dim3(R), dim3(512), tab_lds(reinterpret_cast<const void*>(&row_lse_kernel<1>), tab, attr_row_lse_kernel1), st, logits, lse, V, cap,
-                     emulate_bf16, tab);
-  else
-    hipLaunchKernelGGL(row_lse_kernel<ROW_UNR>, dim3(R), dim3(512), tab_lds(reinterpret_cast<const void*>(&row_lse_kernel<ROW_UNR>), tab, attr_row_lse_kernel), st, logits, lse, V, cap,
-                     emulate_bf16, tab);
+  launch_rows<row_lse_kernel>(R, tab, st, logits, lse, V, cap, emulate_bf16, tab);
 }
 
 void tb_gather_probs(const uint16_t* logits, const float* lse, const int32_t* ids, float* out, int R, int K, int V,
@@ -1258,11 +1132,5 @@ void tb_xent_rows(const uint16_t* logits, const int32_t* tgt, float* nll, int R,
                   hipStream_t st) {
   if (R <= 0) return;
   const uint16_t* tab = find_tab(cap, emulate_bf16);
-  static bool attr_xent_rows_kernel = false, attr_xent_rows_kernel1 = false;
-  if (row_unr() == 1)
-    hipLaunchKernelGGL(xent_rows_kernel<1>, dim3(R), dim3(512), tab_lds(reinterpret_cast<const void*>(&xent_rows_kernel<1>), tab, attr_xent_rows_kernel1), st, logits, tgt, nll, V,
-                     cap, emulate_bf16, tab);
-  else
-    hipLaunchKernelGGL(xent_rows_kernel<ROW_UNR>, dim3(R), dim3(512), tab_lds(reinterpret_cast<const void*>(&xent_rows_kernel<ROW_UNR>), tab, attr_xent_rows_kernel), st, logits, tgt, nll, V,
-                     cap, emulate_bf16, tab);
+  launch_rows<xent_rows_kernel>(R, tab, st, logits, tgt, nll, V, cap, emulate_bf16, tab);
 }

@@ -355,9 +355,10 @@ def _head_outs(fill: bool, dev, R: int) -> Dict[str, torch.Tensor]:
             "nll_tgt": torch.full((R,), NAN, device=dev)}
 
 
-def _check_head(rep, tag, impl, g, dev, z_ref, tgt, cap, labels, stats_off: Optional[int], fill: bool = False) -> None:
+def _check_head(rep, tag, impl, g, dev, z_ref, tgt, cap, labels, stats_off: Optional[int], fill: bool = False):
     """decode_head (and, with ``stats_off`` and a cap the fixed-offset kernel takes, decode_head_stats) on the device
-    rows ``g`` against the float64 row reference ``z_ref`` with teacher targets ``tgt``."""
+    rows ``g`` against the float64 row reference ``z_ref`` with teacher targets ``tgt``.  Returns decode_head's
+    ``nll_tgt``."""
     V = g.shape[-1]
     R = g.shape[0]
     fixed = 0 < cap <= FIXED_CAP_MAX
@@ -369,24 +370,30 @@ def _check_head(rep, tag, impl, g, dev, z_ref, tgt, cap, labels, stats_off: Opti
     check_lse(rep, f"decode_head nll_self {tag}", ns, z_ref["lse"] - z_ref["cmax"], bound, labels)
     check_lse(rep, f"decode_head nll_tgt {tag}", nt, z_ref["lse"] - ct, bound, labels, exact0=~ok)
     if stats_off is None or not fixed:
-        return
+        return nt
     # global targets: local -1 alternates between -1 and an id just below this slice, local V lies beyond it
     tg = torch.where(tgt < 0, torch.where(torch.arange(tgt.numel()) % 2 == 0, -1, stats_off - 1), tgt + stats_off)
     st = impl.decode_head_stats(g, tg.to(torch.int32).to(dev), stats_off, cap, **_f32(fill, dev, R, 4))
     if st is None:
         rep.fail(f"decode_head_stats {tag}: returned None")
-        return
+        return nt
     st = _cpu(st)
     check_lse(rep, f"decode_head_stats lse {tag}", st[:, 0], z_ref["lse"], bound, labels)
     check_exact(rep, f"decode_head_stats best {tag}", st[:, 1], z_ref["cmax"], labels)
     check_exact(rep, f"decode_head_stats id {tag}", st[:, 2], (z_ref["amax"] + stats_off).double(), labels)
     check_exact(rep, f"decode_head_stats target {tag}", st[:, 3],
                 torch.where(ok, ct, torch.full_like(ct, -math.inf)), labels)
+    return nt
 
 
-def run_stream(impl, dev, V: int, caps: Sequence[float] = CAPS, fill: bool = False) -> Report:
+def run_stream(impl, dev, V: int, caps: Sequence[float] = CAPS, fill: bool = False, bits: bool = False) -> Report:
     """argmax_rows, row_lse and xent_rows (``emulate_bf16`` both ways), decode_head and decode_head_stats on
-    :func:`stream_rows` at every cap.  ``fill``: hand every call sentinel-filled outputs (``ops`` only)."""
+    :func:`stream_rows` at every cap.  ``fill``: hand every call sentinel-filled outputs (``ops`` only).  ``bits``
+    (``ops`` only; the reference sums in another order): also the identities that hold because the kernels share one
+    row pass -- under ``emulate_bf16`` (and either way at cap 0) xent_rows is row_lse minus the capped target logit
+    (the bf16 value itself at cap 0, ``ops.softcap_values`` otherwise) and exactly 0 for a target out of range, and
+    where decode_head keeps a running maximum (no cap, or one above ``FIXED_CAP_MAX``) its ``nll_tgt`` is that
+    xent_rows; all bit for bit."""
     rep = Report()
     z, labels, _tie = stream_rows(V)
     g = z.to(dev)
@@ -395,20 +402,31 @@ def run_stream(impl, dev, V: int, caps: Sequence[float] = CAPS, fill: bool = Fal
         r1 = stream_ref(V, cap, True)
         ao = {"out": torch.full((R,), -7, dtype=torch.int32, device=dev)} if fill else {}
         check_ints(rep, f"argmax_rows cap {cap:g}", impl.argmax_rows(g, cap, **ao), r1["amax"], labels)
+        xent_emu = {}
         for emu in (True, False):
             rr = stream_ref(V, cap, emu)
             tag = f"cap {cap:g} emulate {int(emu)}"
             bound = lse_bound(rr["lse"], rr["span_online"], cap, emu)
-            check_lse(rep, f"row_lse {tag}", impl.row_lse(g, cap, emu, **_f32(fill, dev, R)), rr["lse"], bound, labels)
+            lse = impl.row_lse(g, cap, emu, **_f32(fill, dev, R))
+            check_lse(rep, f"row_lse {tag}", lse, rr["lse"], bound, labels)
             for j in (0, 1):
                 tgt = stream_targets(V, cap, j)
                 ok = (tgt >= 0) & (tgt < V)
                 ct = torch.gather(rr["c"], 1, tgt.long().clamp(0, V - 1)[:, None])[:, 0]
-                check_lse(rep, f"xent_rows {tag}", impl.xent_rows(g, tgt.to(dev), cap, emu, **_f32(fill, dev, R)),
-                          rr["lse"] - ct, bound, labels, exact0=~ok)
+                x = impl.xent_rows(g, tgt.to(dev), cap, emu, **_f32(fill, dev, R))
+                check_lse(rep, f"xent_rows {tag}", x, rr["lse"] - ct, bound, labels, exact0=~ok)
+                if emu:
+                    xent_emu[j] = x
+                if bits and (emu or not cap > 0):
+                    zt = torch.gather(g, 1, tgt.long().clamp(0, V - 1)[:, None].to(dev))[:, 0]
+                    want = torch.where(ok, _cpu(lse) - _cpu(_ops.softcap_values(zt, cap)), torch.zeros(R))
+                    check_bits(rep, f"xent_rows {tag} target pass {j}: row_lse minus the capped target logit", x, want)
         for j in (0, 1):
-            _check_head(rep, f"cap {cap:g}", impl, g, dev, r1, stream_targets(V, cap, j), cap, labels,
-                        STATS_OFF if j == 0 else None, fill)
+            nt = _check_head(rep, f"cap {cap:g}", impl, g, dev, r1, stream_targets(V, cap, j), cap, labels,
+                             STATS_OFF if j == 0 else None, fill)
+            if bits and not 0 < cap <= FIXED_CAP_MAX:
+                check_bits(rep, f"decode_head nll_tgt cap {cap:g} target pass {j}: xent_rows emulate 1", nt,
+                           xent_emu[j])
     return rep
 
 

@@ -22,8 +22,9 @@ pytestmark = pytest.mark.gpu
 def test_streamed_readouts(gpu, V):
     """argmax_rows, row_lse / xent_rows (``emulate_bf16`` both ways), decode_head and decode_head_stats at caps 30, 50
     and 0 on random, planted-maximum, saturated-tie, constant, far-negative and lens-like rows; targets -1, V, 0,
-    V - 1, a tail column, a tie member and the argmax."""
-    rd.run_stream(ops, gpu, V, fill=True).assert_ok(f"V {V}")
+    V - 1, a tail column, a tie member and the argmax; and the bit identities of kernels that share one row pass
+    (xent_rows = row_lse - capped target logit; the running-max decode_head's nll_tgt = xent_rows)."""
+    rd.run_stream(ops, gpu, V, fill=True, bits=True).assert_ok(f"V {V}")
 
 
 def test_decode_head_more_rows_than_workgroups(gpu):
