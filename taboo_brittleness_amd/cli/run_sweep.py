@@ -34,8 +34,14 @@ def main(argv=None):
                     help="also record the KL divergence between each cell's and its baseline's next-token distribution "
                          "over the teacher-forced response (intervention.output_shift; needs layer resume; no fused "
                          "head, TP or decode-tail carry-over)")
+    ap.add_argument("--layer-trace", action="store_true",
+                    help="also record the capped lens logit of the tracked ids at every block from the hooked layer on, "
+                         "for each cell and its baseline over the teacher-forced response (intervention.layer_trace; "
+                         "needs layer resume; no TP or decode-tail carry-over)")
     args = ap.parse_args(argv)
     cfg, dev = setup(args)
+    if args.layer_trace:
+        cfg.intervention.layer_trace = True
     if args.forcing:
         cfg.intervention.measure_forcing = True
     if args.output_readout:

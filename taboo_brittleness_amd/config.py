@@ -156,6 +156,11 @@ class InterventionCfg:
     # baseline's rows); adds the ``kl_out_*`` record fields, curves and fig5_collateral.  Needs layer resume; off:
     # records, files and launched kernels are what they are without it.
     output_shift: bool = False
+    # layer trace (opt-in): the capped logit-lens logit of the tracked ids at every block from the hooked layer to the
+    # last, over the teacher-forced response, for each cell and for its baseline (ops.lens_track in hooks of the tail's
+    # packed pass); adds the ``trace_*`` record fields, curves, sweep_trace.csv and fig6_layer_trace.  Needs layer
+    # resume; off: records, files and launched kernels are what they are without it.
+    layer_trace: bool = False
     score_over: str = "prompt"          # "prompt" (per prompt) or "word" (average over prompts)
     # how the targeted latents are ranked: "corr" (EP:118-124: spike-mean activation x positive correlation with the
     # secret probability), or by what ablating the latent alone does at the spikes: "effect_lens" (the exact drop of

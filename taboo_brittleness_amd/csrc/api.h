@@ -147,6 +147,11 @@ void tb_latent_score(const float* acts, const float* p, const uint8_t* spike, co
 void tb_latent_effect(const float* acts, const uint16_t* X, const float* V, int v_per_row, const void* Wdec,
                       int table_f32, const int32_t* seg, float* score, float* eff, int R, int G, int L, int D,
                       double alpha, double eps, double cap, int mode, hipStream_t st);
+// lens_track.hip: out[r, t] = f((h_r . V[vrow[r], t]) / sqrt(|h_r|^2 / D + eps)) for h [M, D] bf16, V [U, T, D] fp32,
+// vrow [M] int32 (outside [0, U): the row's T outputs are 0.0 and no table row is read), f the softcap (cap <= 0:
+// identity); latent_effect's mode-0 numerics, batch-invariant.  0 = launched; 3 = T / D out of range.
+int tb_lens_track(const uint16_t* h, const float* V, const int32_t* vrow, float* out, int M, int U, int T, int D,
+                  double eps, double cap, hipStream_t st);
 // p2p.hip
 int tb_p2p_header_bytes();
 int tb_p2p_max_ranks();

@@ -1054,6 +1054,23 @@ void latent_effect(torch::Tensor acts, torch::Tensor X, torch::Tensor V, torch::
                    (int)mode, cur_stream());
 }
 
+// layer trace (lens_track.hip): h [M, D] bf16, V [U, T, D] f32, vrow [M] int32 -> out [M, T] f32
+void lens_track(torch::Tensor h, torch::Tensor V, torch::Tensor vrow, torch::Tensor out, double eps, double cap) {
+  IN_BF16(h); IN_F32(V); IN_I32(vrow); IN_F32(out);
+  TORCH_CHECK(h.dim() == 2 && V.dim() == 3 && V.size(2) == h.size(1), "lens_track: h [M, D] and V [U, T, D] must share D");
+  const int64_t M = h.size(0), D = h.size(1), U = V.size(0), T = V.size(1);
+  TORCH_CHECK(D % 8 == 0 && D >= 8 && D <= 4096, "lens_track: D must be a multiple of 8 and at most 4096, not ", D);
+  TORCH_CHECK(T >= 1 && T <= 8, "lens_track: 1 <= T <= 8, not ", T);
+  TORCH_CHECK(M < (1LL << 31) / 16 * 16 && U < (1LL << 31) / (T * D), "lens_track: sizes");
+  TORCH_CHECK(vrow.numel() == M && out.numel() == M * T, "lens_track: vrow must be [M] and out [M, T]");
+  TORCH_CHECK(V.device() == h.device() && vrow.device() == h.device() && out.device() == h.device(),
+              "lens_track: one device");
+  c10::DeviceGuard g(h.device());
+  const int rc = tb_lens_track(cbf(h), V.data_ptr<float>(), vrow.data_ptr<int32_t>(), out.data_ptr<float>(), (int)M,
+                               (int)U, (int)T, (int)D, eps, cap, cur_stream());
+  TORCH_CHECK(rc == 0, "lens_track: bad arguments");
+}
+
 int64_t attention_lds_bytes(int64_t hd) { return tb_attention_lds_bytes((int)hd); }
 
 // ---- one-shot P2P all-reduce (p2p.hip): regions are raw device pointers passed as int64
@@ -1332,6 +1349,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flag_compact", &flag_compact);
   m.def("latent_score", &latent_score);
   m.def("latent_effect", &latent_effect);
+  m.def("lens_track", &lens_track);
   m.def("attention_lds_bytes", &attention_lds_bytes);
   m.def("p2p_alloc", &p2p_alloc);
   m.def("p2p_free", &p2p_free);

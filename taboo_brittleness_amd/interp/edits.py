@@ -59,6 +59,10 @@ interpolates between the row's own activations (0) and the donor's (1); ``proj_s
 coordinates outright, as ``proj`` rows are projected out outright.  A row that equals its donor row is an exact
 no-op.  A swap row needs a donor per spike, so it cannot edit at ``ALL_POSITIONS``, and ``sae_swap`` is defined for
 the error-preserving mode only.  A plan without swap rows runs exactly the calls it ran before these kinds existed.
+
+:class:`TraceHook` edits nothing: listed at the hooked layer behind the edit hook and at every later block of a packed
+pass, it reads out the capped lens logit of each row's tracked tokens (``ops.lens_track``), the layer trace of the
+sweep (``intervention.layer_trace``).
 """
 from __future__ import annotations
 
@@ -405,3 +409,64 @@ class CaptureHook:
 
     def __call__(self, h: torch.Tensor, x: torch.Tensor, ctx) -> None:
         ops.capture_rows(self.store, h, ctx.pos, ctx.slot, ctx.B, ctx.T)
+
+
+class TraceHook:
+    """Layer trace: the tracked tokens' capped lens logits of the residual rows at every block from ``first`` on
+    (``ops.lens_track``).  Holds the launch's table ``V [U, T, D]`` fp32 (one block of lens directions per pair), the
+    row map ``rows [M]`` int32 (the table block of every row of the launch) and the output ``out [Lt, M, T]`` fp32,
+    ``Lt`` blocks from ``first``; one instance is listed at each of those blocks, at block ``first`` after the edit
+    hook, so it sees the edited rows.  A call at block ``l`` reads the rows of the current window into slab
+    ``l - first``.
+
+    A packed forward runs one chunk of the launch's rows, padded to whole GEMM tiles: :meth:`use_rows` sets the
+    chunk's window ``[r0, r1)`` before each forward (as :meth:`EditHook.use_table` sets the splice table), and builds
+    the chunk's map -- its rows' table blocks, -1 on the padding rows, which the kernel skips.  Shapes are static
+    per chunk and nothing syncs with the host."""
+
+    def __init__(self, V: torch.Tensor, rows: torch.Tensor, out: torch.Tensor, first: int, eps: float, cap: float):
+        if V.dim() != 3 or out.dim() != 3 or out.shape[1] != rows.shape[0] or out.shape[2] != V.shape[1]:
+            raise ValueError(f"TraceHook: V [U, T, D], rows [M] and out [Lt, M, T] do not fit: {tuple(V.shape)}, "
+                             f"{tuple(rows.shape)}, {tuple(out.shape)}")
+        if rows.dtype != torch.int32:
+            raise ValueError("TraceHook: rows must be int32")
+        self.V, self.rows, self.out = V, rows, out
+        self.first, self.eps, self.cap = int(first), float(eps), float(cap)
+        self.calls = 0
+        self.use_rows(0, rows.shape[0])
+
+    @property
+    def layers(self) -> range:
+        return range(self.first, self.first + self.out.shape[0])
+
+    def use_rows(self, r0: int, r1: int, padded: Optional[int] = None) -> None:
+        """The next forwards run rows ``[r0, r1)`` of the launch, followed by padding rows up to ``padded`` rows."""
+        n = r1 - r0
+        padded = n if padded is None else int(padded)
+        if not 0 <= r0 <= r1 <= self.rows.shape[0] or padded < n:
+            raise ValueError(f"TraceHook.use_rows: window [{r0}, {r1}) padded to {padded} does not fit "
+                             f"{self.rows.shape[0]} rows")
+        self._win = (r0, r1)
+        if padded == n:
+            self._map, self._tmp = self.rows[r0:r1], None
+        else:
+            self._map = torch.full((padded,), -1, dtype=torch.int32, device=self.rows.device)
+            self._map[:n].copy_(self.rows[r0:r1])
+            self._tmp = torch.empty(padded, self.out.shape[2], dtype=torch.float32, device=self.rows.device)
+
+    def __call__(self, h: torch.Tensor, x: torch.Tensor, ctx) -> None:
+        k = ctx.layer - self.first
+        if not 0 <= k < self.out.shape[0]:
+            raise ValueError(f"TraceHook: called at block {ctx.layer}, traces blocks {self.first}.."
+                             f"{self.first + self.out.shape[0] - 1}")
+        r0, r1 = self._win
+        hv = h.view(-1, h.shape[-1])
+        if hv.shape[0] != self._map.shape[0]:
+            raise ValueError(f"TraceHook: the forward has {hv.shape[0]} rows, the window set by use_rows "
+                             f"{self._map.shape[0]}")
+        self.calls += 1
+        if self._tmp is None:
+            ops.lens_track(hv, self.V, self._map, self.eps, self.cap, out=self.out[k, r0:r1])
+        else:
+            ops.lens_track(hv, self.V, self._map, self.eps, self.cap, out=self._tmp)
+            self.out[k, r0:r1].copy_(self._tmp[: r1 - r0])

@@ -893,3 +893,42 @@ def latent_effect(acts, X, V, Wdec, seg, alpha, eps, cap, mode, want_eff=False):
         return (score, eff) if want_eff else score
     score, eff = ref.latent_effect(acts, X, V, Wdec, seg, alpha, eps, cap, int(mode))
     return (score.float(), eff.float()) if want_eff else score.float()
+
+
+LENS_TRACK_MAX = 8      # tracked columns of lens_track (csrc/lens_track.hip: one kernel instance per T)
+
+
+def lens_track(h, V, vrow, eps, cap, out=None):
+    """Tracked-token lens logits of residual rows (csrc/lens_track.hip): ``out[r, t] = f((h_r . V[vrow[r], t]) /
+    sqrt(|h_r|^2 / D + eps))`` for ``h [M, D]`` bf16, a table ``V [U, T, D]`` fp32 of lens directions
+    (``interp/gradient.py::lens_direction``), a row map ``vrow [M]`` int32 and ``f`` the softcap ``cap tanh(. / cap)``
+    (``cap <= 0``: identity).  A row with ``vrow[r]`` outside ``[0, U)`` gets 0.0 in all ``T`` columns and reads no
+    table row; an all-zero table row gives exactly 0.0.  A row's bits depend on that row and its table block alone
+    (not on ``M``, its place in the call or the other rows' ``vrow``).  ``D % 8 == 0``, ``D <= 4096``,
+    ``1 <= T <= 8``; anything else raises ``ValueError``.  Returns ``out [M, T]`` fp32."""
+    if h.dim() != 2 or V.dim() != 3 or V.shape[2] != h.shape[1]:
+        raise ValueError(f"lens_track: h [M, D] and V [U, T, D] must share D, got {tuple(h.shape)} and {tuple(V.shape)}")
+    M, D = h.shape
+    U, T = V.shape[0], V.shape[1]
+    if D % 8 != 0 or not 8 <= D <= 4096:
+        raise ValueError(f"lens_track: D must be a multiple of 8 and at most 4096, not {D}")
+    if not 1 <= T <= LENS_TRACK_MAX:
+        raise ValueError(f"lens_track: 1 <= T <= {LENS_TRACK_MAX} tracked columns, not {T}")
+    if h.dtype != BF16 or V.dtype != torch.float32:
+        raise ValueError(f"lens_track: h must be bf16 and V float32, got {h.dtype} and {V.dtype}")
+    if vrow.dtype != torch.int32 or vrow.dim() != 1 or vrow.shape[0] != M:
+        raise ValueError(f"lens_track: vrow must be [M={M}] int32, got {tuple(vrow.shape)} {vrow.dtype}")
+    dev = h.device
+    if V.device != dev or vrow.device != dev:
+        raise ValueError("lens_track: h, V and vrow must be on one device")
+    if out is not None and (out.shape != (M, T) or out.dtype != torch.float32 or out.device != dev
+                            or not out.is_contiguous()):
+        raise ValueError(f"lens_track: out must be a contiguous [M={M}, T={T}] float32 on h's device")
+    out = _out(out, (M, T), torch.float32, dev)
+    if M == 0:
+        return out
+    if h.is_cuda:
+        _k().lens_track(h.contiguous(), V.contiguous(), vrow.contiguous(), out, float(eps), float(cap))
+        return out
+    out.copy_(ref.lens_track(h, V, vrow, eps, cap))
+    return out

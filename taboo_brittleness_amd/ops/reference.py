@@ -603,6 +603,26 @@ def latent_effect(acts: torch.Tensor, X: torch.Tensor, V: torch.Tensor, Wdec: to
     return score, eff
 
 
+def lens_track(h: torch.Tensor, V: torch.Tensor, vrow: torch.Tensor, eps: float, cap: float) -> torch.Tensor:
+    """Reference of ``ops.lens_track`` in fp64, as the explicit formula: ``out[r, t] = f((h_r . V[vrow[r], t]) /
+    sqrt(|h_r|^2 / D + eps))`` with ``f = cap tanh(. / cap)`` (``cap <= 0``: identity).  Rows with ``vrow[r]`` outside
+    ``[0, U)`` are 0.  ``[M, T]`` fp64."""
+    M, D = h.shape
+    U, T = V.shape[0], V.shape[1]
+    eps, cap = float(eps), float(cap)
+    hd, Vd = h.double(), V.double()
+    u = vrow.long()
+    ok = (u >= 0) & (u < U)
+    out = torch.zeros(M, T, dtype=torch.float64, device=h.device)
+    rows = torch.nonzero(ok).flatten()
+    for i0 in range(0, rows.numel(), 512):       # elementwise products summed per (row, t): no row sees another
+        r = rows[i0:i0 + 512]
+        x = hd[r]
+        z = (x[:, None, :] * Vd[u[r]]).sum(-1) / torch.sqrt(x.pow(2).sum(-1) / D + eps)[:, None]
+        out[r] = cap * torch.tanh(z / cap) if cap > 0 else z
+    return out
+
+
 def vp_head_merge(st: torch.Tensor, tgt, V: int):
     """Reference of ``ops.vp_head_merge`` (rank order; on equal best logits the lower rank = lower vocab id)."""
     tp, R = st.shape[0], st.shape[1]

@@ -51,6 +51,9 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
         raise ValueError("intervention.output_readout has no tensor-parallel version (parallel.tp > 1): run it with tp = 1")
     if cfg.intervention.output_shift and cfg.parallel.tp > 1:
         raise ValueError("intervention.output_shift has no tensor-parallel version (parallel.tp > 1): run it with tp = 1")
+    if cfg.intervention.layer_trace and cfg.parallel.tp > 1:
+        raise ValueError("intervention.layer_trace has no tensor-parallel version (parallel.tp > 1): run it with "
+                         "tp = 1")
     info = info or D.init_distributed(cfg.parallel.backend, cfg.runtime.device)
     tp_ctx, dp_rank, dp_size = None, info.rank, info.world
     if cfg.parallel.tp > 1:
@@ -163,6 +166,9 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
             summary["config"]["output_readout"] = True
         if runner.output_shift:
             summary["config"]["output_shift"] = True
+        if runner.layer_trace:
+            summary["config"]["layer_trace"] = True
+            summary["config"]["trace_blocks"] = list(range(stack.layer, model.spec.layers))
         if swap:
             summary["config"]["swap_donor"] = runner.swap_donor
             summary["swap_skipped"] = [{"word": w, "prompt_idx": i} for w, i in runner.swap_skipped]
@@ -186,6 +192,15 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
                 ll.get("prompt_accuracy", ""), ll.get("any_pass", ""), ll.get("global_majority_vote", "")] +
                 [c[k][q] for k in ro_cols for q in ("mean", "lo", "hi")]))
         atomic_write_text(os.path.join(out_dir, "sweep_curves.csv"), "\n".join(lines) + "\n")
+        if runner.layer_trace:                       # one line per (method, budget, block)
+            tl = ["method,budget,n,block,trace_dz_spike,trace_dz_spike_lo,trace_dz_spike_hi,trace_recovery,"
+                  "trace_recovery_lo,trace_recovery_hi"]
+            for c in summary["curves"]:
+                rc = c["trace_recovery"]
+                for blk, ci in zip(summary["config"]["trace_blocks"], c["trace_dz_spike"]):
+                    tl.append(",".join(str(x) for x in [c["method"], c["budget"], c["n"], blk, ci["mean"], ci["lo"],
+                                                        ci["hi"], rc["mean"], rc["lo"], rc["hi"]]))
+            atomic_write_text(os.path.join(out_dir, "sweep_trace.csv"), "\n".join(tl) + "\n")
         sw = [c for c in summary["curves"] if "p_donor_mean" in c]
         if sw:
             sl = ["method,budget,n,p_secret_mean,delta_p,p_donor_mean,p_donor_lo,p_donor_hi,delta_p_donor,"

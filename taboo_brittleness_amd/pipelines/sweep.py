@@ -69,6 +69,13 @@ coincide with the target's row where their spikes coincide: that spike is an exa
 lens logit, or its first-order attribution to the model's own logit); cells, seeds, random pools and every reuse
 level are those of the default ``corr``.
 
+``intervention.layer_trace`` (opt-in) reads the blocks between the edit and the output: the teacher-forced tail and the
+pairs' unedited pass of blocks ``l+1..`` carry a :class:`~..interp.edits.TraceHook` at blocks ``l .. layers - 1`` that
+writes the capped lens logit of every row's tracked ids (``ops.lens_track``); the records' ``trace_*`` fields are the
+per-block differences edited minus baseline at the spikes and over the response, and ``trace_recovery``, the share of
+the direct effect that the later blocks undo.  Teacher-forced rows only: the decode rows of diverged cells are not
+traced, and the decode hipGraphs never see the hook.
+
 Module layout: this module holds the runner's driver (construction, baselines, ``run_cells``) and the
 summaries; its methods are grouped by phase into mixins -- :mod:`.sweep_plan` (pair scoring, cells, edit bases
 and plans, prefetch), :mod:`.sweep_decode` (one batch through the decode: layer resume, prefix-trie keys,
@@ -151,6 +158,16 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
             if not 0.0 < cap <= 40.0:
                 raise ValueError(f"intervention.output_shift needs a final softcap in (0, 40] (the shift kernel's "
                                  f"range), not {cap}")
+        # layer trace (intervention.layer_trace): the teacher-forced tail and the pairs' unedited pass also read out the
+        # tracked ids' capped lens logit at every block from the hooked layer on (ops.lens_track in TraceHooks):
+        # ``trace_*`` fields
+        self.layer_trace = bool(getattr(self.iv, "layer_trace", False))
+        if self.layer_trace:
+            if getattr(model, "tp", None) is not None:
+                raise ValueError("intervention.layer_trace has no tensor-parallel version: run it with tp = 1")
+            if model.spec.hidden % 8 or model.spec.hidden > 4096:
+                raise ValueError(f"intervention.layer_trace needs a residual width that is a multiple of 8 and at most "
+                                 f"4096 (the trace kernel's range), not {model.spec.hidden}")
         self.exclusion = exclusion
         self.use_graphs = use_graphs
         self.prefix_share = cfg.runtime.prefix_share if prefix_share is None else prefix_share
@@ -167,6 +184,9 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
         self.layer_resume = cfg.runtime.layer_resume if layer_resume is None else layer_resume
         if self.output_shift and not (self.layer_resume and self.prefix_share):
             raise ValueError("intervention.output_shift is read from the layer-resumed teacher-forced tail: run it "
+                             "with layer resume and prefix sharing on (no --no-layer-resume / --no-prefix-share)")
+        if self.layer_trace and not (self.layer_resume and self.prefix_share):
+            raise ValueError("intervention.layer_trace is read from the layer-resumed teacher-forced tail: run it "
                              "with layer resume and prefix sharing on (no --no-layer-resume / --no-prefix-share)")
         # the teacher-forced tail reads its pair's baseline prefix K/V in place (False: copies it into each cell's slot)
         self.tf_prefix = True
@@ -233,6 +253,12 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
             # ranked: the secret's two forms and, in a run with swap methods, the other words' secrets (a donor's
             # secret is one of them); Pair.ro_order puts those columns first in the head's id table
             self._n_rank = max(2 + max(len(p.extra) for p in pairs), getattr(self, "_n_rank", 0))
+        if self.layer_trace and pairs:
+            K = max(len(p.track) for p in pairs)
+            if K > ops.LENS_TRACK_MAX:
+                raise ValueError(f"intervention.layer_trace tracks at most {ops.LENS_TRACK_MAX} ids per pair (two "
+                                 f"secret forms, decoys, the other words' secrets for swap runs), not {K}")
+            self._n_trace = max(K, getattr(self, "_n_trace", 0))
         return pairs
 
     def _track_cols(self) -> int:
@@ -374,6 +400,8 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
             raise ValueError("intervention.output_readout does not support the decode-tail carry-over (carry_rows > 0)")
         if self.output_shift and self.carry_rows:
             raise ValueError("intervention.output_shift does not support the decode-tail carry-over (carry_rows > 0)")
+        if self.layer_trace and self.carry_rows:
+            raise ValueError("intervention.layer_trace does not support the decode-tail carry-over (carry_rows > 0)")
         if any(swap) and self.carry_rows:
             raise ValueError("swap cells do not support the decode-tail carry-over (carry_rows > 0): a carried cell's "
                              "donor rows would have to move with it")
@@ -483,6 +511,12 @@ def summarize_cells(results: Sequence[dict], words: Sequence[str], word_plurals:
         if rs and "kl_out_mean" in rs[0]:        # output shift (intervention.output_shift) only
             for i, key in enumerate(("kl_out_mean", "kl_out_spike_mean")):
                 ent[key] = bootstrap_ci([r[key] for r in rs if r[key] == r[key]], seed=bud + 8 + i)
+        if rs and "trace_dz_spike" in rs[0]:     # layer trace (intervention.layer_trace) only: one CI per block
+            Lt = len(rs[0]["trace_dz_spike"])
+            ent["trace_dz_spike"] = [bootstrap_ci([r["trace_dz_spike"][k] for r in rs], seed=bud + 10 + k)
+                                     for k in range(Lt)]
+            ent["trace_recovery"] = bootstrap_ci([r["trace_recovery"] for r in rs
+                                                  if r["trace_recovery"] == r["trace_recovery"]], seed=bud + 10 + Lt)
         if meth in NOISE_METHODS:                # how far the control (= its targeted twin) moved the stream
             ent["edit_norm"] = float(np.mean([r["edit_norm"] for r in rs]))
         if meth in SWAP_METHODS:                 # what the transplant did to the donor's secret

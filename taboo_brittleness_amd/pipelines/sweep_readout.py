@@ -12,7 +12,7 @@ import torch
 
 from .. import ops
 from ..interp import analysis as A
-from ..interp.edits import EditHook
+from ..interp.edits import EditHook, TraceHook
 from ..interp.logit_lens import excl_table, lens_packed, lens_readout, reference_exclusions, vocab_slice, vocab_topk
 from ..interp.prompts import contains_secret
 from .sweep_types import NOISE_METHODS, SWAP_METHODS, Cell, Pair, _h2d, _nullctx
@@ -164,6 +164,9 @@ class ReadoutMixin:
         if self.output_shift:
             # the tail's per-row KLs against the baseline rows; a cell's rows start at r0 (tail row f)
             cols["shift"] = {"kl": tf.get("kl"), "kl_rev": tf.get("kl_rev"), "r0": tf["r0"][slot_a], "f": f_e}
+        if self.layer_trace:
+            # the tail's [Lt, M, T] lens logits; a cell's rows f .. E start at r0
+            cols["trace"] = {"z": tf.get("trace"), "r0": tf["r0"][slot_a], "f": f_e, "E": tf["E"][slot_a]}
         if getattr(self, "_defer", False):
             return self._records_pool().submit(self._resume_records, batch, cell_pairs, cols, pr, vh, ih, K)
         return self._resume_records(batch, cell_pairs, cols, pr, vh, ih, K)
@@ -246,6 +249,7 @@ class ReadoutMixin:
         results = []
         ro = cols.get("ro")
         sft = cols.get("shift")
+        trc = cols.get("trace")
         for b, (c, p) in enumerate(zip(batch, cell_pairs)):
             ng = int(ng_a[b])
             resp = host_tok[j_a[b], :ng].tolist() if div[b] else p.resp
@@ -264,6 +268,9 @@ class ReadoutMixin:
             if sft is not None:                  # output shift only: the other runs keep their keys
                 results[-1].update(self._shift_fields(p, int(sft["f"][b]), int(sft["r0"][b]), sft["kl"],
                                                       sft["kl_rev"]))
+            if trc is not None:                  # layer trace only: the other runs keep their keys
+                results[-1].update(self._trace_fields(p, int(trc["f"][b]), int(trc["E"][b]), int(trc["r0"][b]),
+                                                      trc["z"], q if c.method in SWAP_METHODS else None))
         return results
 
     @staticmethod
@@ -436,6 +443,10 @@ class ReadoutMixin:
             res["nxt"] = host[0, :M].view(torch.int32).numpy()
             res["nll_self"] = host[1, :M].numpy()
             res["nll_tgt"] = host[2, :M].numpy()
+            tr = res.pop("_trace", None)
+            if tr is not None:               # layer trace: [Lt, M, T] lens logits ride behind everything else
+                res["trace"] = flat[flat.numel() - tr[0] * M * tr[1]:].view(tr[0], M, tr[1]).numpy()
+                flat = flat[: flat.numel() - tr[0] * M * tr[1]]
             if res.pop("_shift", False):     # output shift: the rows' two KLs ride at the buffer's end
                 res["kl"] = flat[flat.numel() - 2 * M: flat.numel() - M].numpy()
                 res["kl_rev"] = flat[flat.numel() - M:].numpy()
@@ -494,7 +505,13 @@ class ReadoutMixin:
         res = {"seg": seg, "nxt": np.zeros(0, np.int32), "nll_self": np.zeros(0, np.float32),
                "nll_tgt": np.zeros(0, np.float32), "row_cell": rb_, "row_t": t_, "tgt": tgt,
                "f": f_a, "E": E_a, "r0": r0_a, "up": up_a, "upairs": [p for p, _ in ulist], "gtab": gtab}
+        trace = self.layer_trace
+        first_cell = {}                      # per unique pair: a cell slot of the running batch
+        for b in range(nc - 1, -1, -1) if (trace or self.output_shift) else ():
+            first_cell[int(up_a[b])] = b
         if M == 0:
+            if trace:                        # no cell has a tail row: the records still report the baseline's trace
+                self._shift_base([p for p, _ in ulist], [first_cell[u] for u in range(len(ulist))], sync=True)
             return res
         dev = self.dev
         up_ = lambda a: _h2d(a, dev).to(dev, non_blocking=True)     # noqa: E731  (pinned: no stream drain)
@@ -507,7 +524,9 @@ class ReadoutMixin:
         # one buffer, one D2H copy
         Kt = self._track_cols()
         shift = self.output_shift
-        flat = torch.empty(3 * M + 2 * M * Kt + (2 * M if shift else 0), dtype=torch.float32, device=dev)
+        Lt, Tt = (m.spec.layers - self.layer, self._n_trace) if trace else (0, 0)
+        n_tr = Lt * M * Tt                   # layer trace: [Lt, M, Tt] lens logits behind the KLs
+        flat = torch.empty(3 * M + 2 * M * Kt + (2 * M if shift else 0) + n_tr, dtype=torch.float32, device=dev)
         outs = flat[: 3 * M].view(3, M)
         nxt, ns, nt = outs[0].view(torch.int32), outs[1], outs[2]
         ro = None
@@ -563,15 +582,24 @@ class ReadoutMixin:
             tb_d = up_(tb)
             for hk in splice:
                 hk.use_table(acts_tab, tb_d)
-        sh = None
+        sh = tr = None
+        if shift or trace:
+            # the pairs' unedited pass of blocks l+1..: the baseline side of the output shift and of the layer trace
+            Xb = self._shift_base([p for p, _ in ulist], [first_cell[u] for u in range(len(ulist))])
+        if trace:
+            # layer trace: one table block per pair of the launch, every tail row reads its pair's; the hook sits at
+            # blocks l .. layers - 1 of the tail's packed pass, at block l behind the edit hook
+            tr = TraceHook(self._trace_table([p for p, _ in ulist]), up_(up_a[rb_].astype(np.int32)),
+                           flat[flat.numel() - n_tr:].view(Lt, M, Tt), self.layer, m.spec.eps,
+                           float(m.spec.final_softcap or 0.0))
+            hooks = {l: list(hooks.get(l, ())) + ([tr] if l in tr.layers else []) for l in set(hooks) | set(tr.layers)}
+            self.stats["trace_rows"] = self.stats.get("trace_rows", 0) + Lt * M
+            res["_trace"] = (Lt, Tt)
         if shift:
             # output shift: tail row (cell, t) is compared with its pair's unedited row t.  ``src`` already names that
             # row in the concatenation of the pairs' rows; per head sub-chunk the distinct baseline rows and the rows'
             # indices into them go up once, for the whole launch
-            first_cell = {}
-            for b in range(nc - 1, -1, -1):
-                first_cell[int(up_a[b])] = b
-            Xb = self._shift_base([p for p, _ in ulist], [first_cell[u] for u in range(len(ulist))])
+            kl_end = flat.numel() - n_tr
             ub, rmap, uoff = [], np.zeros(M, np.int32), {}
             n_u = 0
             for (c0, c1, _chunk) in chunks:
@@ -584,11 +612,11 @@ class ReadoutMixin:
                     n_u += u.size
             self.stats["shift_base_rows"] = self.stats.get("shift_base_rows", 0) + n_u
             sh = {"x": Xb, "ub": up_(np.concatenate(ub).astype(np.int64)), "map": up_(rmap), "off": uoff,
-                  "kl": flat[flat.numel() - 2 * M: flat.numel() - M], "kl_rev": flat[flat.numel() - M:]}
+                  "kl": flat[kl_end - 2 * M: kl_end - M], "kl_rev": flat[kl_end - M: kl_end]}
             res["_shift"] = True
         try:
             self._tf_chunks(chunks, streams, tab_d, tab_off, pos_d, slot_d, tgt_d, src_d, H, ws_rows, step, hooks,
-                            nxt, ns, nt, ro, sh)
+                            nxt, ns, nt, ro, sh, tr)
         finally:
             for hk in splice:
                 hk.use_table(None)
@@ -606,11 +634,12 @@ class ReadoutMixin:
         return res
 
     def _tf_chunks(self, chunks, streams, tab_d, tab_off, pos_d, slot_d, tgt_d, src_d, H, ws_rows, step, hooks,
-                   nxt, ns, nt, ro=None, sh=None) -> None:
+                   nxt, ns, nt, ro=None, sh=None, tr=None) -> None:
         """The packed forwards + vocab heads of :meth:`_tf_launch`, chunk by chunk.  ``ro`` (output readout): the rows'
         tracked ids ``[M, K]`` and the ``[M, K]`` log-prob / rank outputs of the tracking head.  ``sh`` (output
         shift): the pairs' unedited final-normed rows, per head sub-chunk its distinct baseline rows and the rows'
-        indices into them, and the ``[M]`` KL outputs."""
+        indices into them, and the ``[M]`` KL outputs.  ``tr`` (layer trace): the launch's trace hook, already listed
+        in ``hooks``; it is told every chunk's row window."""
         m, dev = self.m, self.dev
 
         def shift_rows(lg, a, e):
@@ -640,6 +669,8 @@ class ReadoutMixin:
                 ops.row_gather(H, src_d[c0:c1], hin)
                 if Mp > Mc:
                     hin[Mc:].zero_()
+                if tr is not None:
+                    tr.use_rows(c0, c1, Mp)
                 x = m.forward_packed(None, cp, cs, blk, self.gen.cache, hooks, ws=ws, resume_after=self.layer,
                                      h_in=hin, prefix_kv=self.pair_kv if self.tf_prefix else None)
                 for q0 in range(0, Mc, step):
@@ -662,7 +693,7 @@ class ReadoutMixin:
                         shift_rows(lg, c0 + q0, c0 + q1)
 
     @torch.no_grad()
-    def _shift_base(self, upairs: Sequence[Pair], slots: Sequence[int]) -> torch.Tensor:
+    def _shift_base(self, upairs: Sequence[Pair], slots: Sequence[int], sync: bool = False) -> Optional[torch.Tensor]:
         """Output shift: the unedited final-normed rows of ``upairs``, concatenated in their order (``[sum n, D]``, the
         row layout of the concatenated ``Pair.resid``).  A pair's rows come from one packed pass of blocks ``l+1..``
         over its kept hooked-layer rows with no edit hook -- the teacher-forced tail's own path, so in the
@@ -670,12 +701,25 @@ class ReadoutMixin:
         kept on the pair (``Pair.x_base``, the size of ``Pair.resid``) for its later batches.  The pass writes the
         K/V of blocks ``l+1..`` at the response positions of ``slots[u]``, a cell slot of pair ``u`` in the running
         batch: the tail rewrites what it reads of them, and the decode reads the positions below a cell's first
-        edit from the pair's own K/V."""
+        edit from the pair's own K/V.
+
+        Layer trace: the same pass carries the tail's trace hook at blocks ``l .. layers - 1`` and keeps the pair's
+        ``[n, Lt, T]`` lens logits on the host (``Pair.z_base``, a few KB; their copy is asynchronous on the GPU and
+        finished by the time the launch's own D2H event has passed, or on return with ``sync``).  With the trace
+        alone the final-normed rows are not kept and nothing is returned; with the output shift alone the pass is
+        what it was."""
         from ..models.gemma2 import packed_blocks
 
         m, dev = self.m, self.dev
+        shift, trace = self.output_shift, self.layer_trace
+        stale = lambda v, p: v is None or v[0] is not p.resid      # noqa: E731
         need = [(p, s) for p, s in zip(upairs, slots)
-                if (p.x_base is None or p.x_base[0] is not p.resid) and p.resid.shape[0]]
+                if ((shift and stale(p.x_base, p)) or (trace and stale(p.z_base, p))) and p.resid.shape[0]]
+        if trace:
+            Lt, Tt = m.spec.layers - self.layer, self._n_trace
+            for p in upairs:                 # an empty response has an empty trace
+                if not p.resid.shape[0] and stale(p.z_base, p):
+                    p.z_base = (p.resid, torch.zeros(0, Lt, Tt))
         rpb = 16 // max(1, m.lspec.heads // m.lspec.kv_heads)
         i = 0
         while i < len(need):
@@ -697,18 +741,43 @@ class ReadoutMixin:
             hin[:rows].copy_(torch.cat([p.resid for p, _ in grp], 0) if len(grp) > 1 else grp[0][0].resid)
             if Mp > rows:
                 hin[rows:].zero_()
+            hooks = tr = None
+            if trace:
+                vrow = np.repeat(np.arange(len(grp), dtype=np.int32), [p.resid.shape[0] for p, _ in grp])
+                tr = TraceHook(self._trace_table([p for p, _ in grp]), _h2d(vrow, dev).to(dev, non_blocking=True),
+                               torch.empty(Lt, rows, Tt, dtype=torch.float32, device=dev), self.layer, m.spec.eps,
+                               float(m.spec.final_softcap or 0.0))
+                tr.use_rows(0, rows, Mp)
+                hooks = {l: [tr] for l in tr.layers}
             x = m.forward_packed(None, _h2d(pos, dev).to(dev, non_blocking=True),
                                  _h2d(slot, dev).to(dev, non_blocking=True),
-                                 _h2d(packed_blocks(seqs, rpb), dev).to(dev, non_blocking=True), self.gen.cache, None,
+                                 _h2d(packed_blocks(seqs, rpb), dev).to(dev, non_blocking=True), self.gen.cache, hooks,
                                  ws=ws, resume_after=self.layer, h_in=hin,
                                  prefix_kv=self.pair_kv if self.tf_prefix else None)
-            xs = x[:rows].clone()
+            xs = x[:rows].clone() if shift else None
+            zs = None
+            if trace:
+                zd = tr.out.permute(1, 0, 2).contiguous()                 # [rows, Lt, Tt]
+                if dev.type == "cuda":
+                    zs = torch.empty(zd.shape, dtype=torch.float32, pin_memory=True)
+                    zs.copy_(zd, non_blocking=True)
+                else:
+                    zs = zd
+                self.stats["trace_base_rows"] = self.stats.get("trace_base_rows", 0) + Lt * rows
             r0 = 0
             for p, _ in grp:
                 n = p.resid.shape[0]
-                p.x_base = (p.resid, xs[r0:r0 + n])
+                if shift:
+                    p.x_base = (p.resid, xs[r0:r0 + n])
+                if trace:
+                    p.z_base = (p.resid, zs[r0:r0 + n])
                 r0 += n
-            self.stats["shift_base_pass_rows"] = self.stats.get("shift_base_pass_rows", 0) + rows
+            if shift:
+                self.stats["shift_base_pass_rows"] = self.stats.get("shift_base_pass_rows", 0) + rows
+        if trace and sync and dev.type == "cuda":
+            torch.cuda.current_stream(dev).synchronize()
+        if not shift:
+            return None
         parts = [p.x_base[1] if p.resid.shape[0] else p.resid.new_zeros(0, self.D) for p in upairs]
         return torch.cat(parts, 0) if len(parts) > 1 else parts[0]
 
@@ -734,6 +803,68 @@ class ReadoutMixin:
                 "kl_out_max": max([0.0] + rows.tolist()),
                 "kl_out_spike_mean": math.fsum(hit) / len(sp) if sp else 0.0,
                 "kl_rev_out_mean": math.fsum(rrev.tolist()) / n if n else 0.0}
+
+    def _trace_table(self, upairs: Sequence[Pair]) -> torch.Tensor:
+        """Layer trace: the ``[U, T, D]`` fp32 table of lens directions, one block per pair, its columns in
+        ``Pair.track`` order (``T`` = the run's widest track list; columns a pair does not have, and ids outside the
+        vocabulary, are zero rows, which read out as exactly 0).  Each row is ``lens_direction`` of that single id; a
+        pair's block is built once per runner."""
+        from ..interp.gradient import lens_direction
+
+        T = self._n_trace
+        cache = self.__dict__.setdefault("_trace_blocks", {})
+        V = self.m.spec.vocab_size
+        out = []
+        for p in upairs:
+            key = tuple(int(t) for t in p.track)
+            blk = cache.get(key)
+            if blk is None or blk.shape[0] != T:
+                blk = torch.zeros(T, self.D, dtype=torch.float32, device=self.dev)
+                for j, t in enumerate(key):
+                    if 0 <= t < V:
+                        blk[j] = lens_direction(self.m, [t]).to(self.dev)
+                cache[key] = blk
+            out.append(blk)
+        return torch.stack(out, 0).contiguous()
+
+    def _trace_fields(self, p: Pair, f: int, E: int, r0: int, z: Optional[np.ndarray],
+                      donor: Optional[Pair] = None) -> dict:
+        """Record fields of the layer trace for a cell whose teacher-forced tail holds response rows ``f..E`` from row
+        ``r0`` of ``z [Lt, M, T]`` (the capped lens logit of the pair's tracked ids at blocks ``l .. layers - 1``;
+        column 0 is the secret).  Every field but ``trace_recovery`` is a list over those blocks.  ``dz`` is the plain
+        difference ``z_edit - z_base`` of the two fp32 values against the pair's unedited pass (``Pair.z_base``), so a
+        row no edit reached differs by exactly 0; rows before ``f`` are the baseline's and are not computed.
+        ``trace_dz_spike`` / ``trace_z_base_spike`` / ``trace_decoy_dz_spike`` / ``trace_dz_donor_spike`` (swap cells:
+        the donor's secret) are means over the pair's spikes ``t`` of row ``t`` itself, the row the edit is written to
+        (spikes before ``f`` were no-op edits: 0); ``trace_dz_mean`` runs over the rows of the cell's ``nll_edit``
+        (``f .. n - 2``) with its denominator ``n``.  ``trace_recovery = 1 - trace_dz_spike[-1] / trace_dz_spike[0]``
+        is the share of the direct effect that the later blocks undo (nan where there is no direct effect).  The sums
+        are exactly rounded (``math.fsum``)."""
+        import math
+
+        Lt = self.m.spec.layers - self.layer
+        n = len(p.resp)
+        zb = p.z_base[1].numpy() if p.z_base is not None else np.zeros((0, Lt, len(p.track)), np.float32)
+        Ln = max(0, min(E, n - 1) - f + 1) if z is not None else 0
+        # dz[k, i, col]: block l + k, response row f + i
+        dz = (z[:, r0:r0 + Ln].astype(np.float64) - zb[f:f + Ln].transpose(1, 0, 2).astype(np.float64)
+              if Ln else np.zeros((Lt, 0, zb.shape[2])))
+        sp = [t for t in p.spikes_rel if t < n]
+        hit = [t - f for t in sp if f <= t < f + Ln]
+        ntail = min(max(0, n - 1 - f), Ln)
+        # per block: an exactly rounded sum over the listed values (one list per block), over a fixed denominator
+        mean = lambda rows, den: [math.fsum(v) / den if den else 0.0 for v in rows.tolist()]      # noqa: E731
+        nd = p.n_decoys
+        dzs = dz[:, hit, :]                                                  # [Lt, spikes at or past f, T]
+        out = {"trace_dz_spike": mean(dzs[:, :, 0], len(sp)),
+               "trace_dz_mean": mean(dz[:, :ntail, 0], n),
+               "trace_z_base_spike": mean(zb[sp, :, 0].T.astype(np.float64), len(sp)),
+               "trace_decoy_dz_spike": mean(dzs[:, :, 2:2 + nd].reshape(Lt, len(hit) * nd), len(sp) * nd)}
+        if donor is not None:
+            out["trace_dz_donor_spike"] = mean(dzs[:, :, p.extra.get(donor.word, 0)], len(sp))
+        d0, d1 = out["trace_dz_spike"][0], out["trace_dz_spike"][-1]
+        out["trace_recovery"] = 1.0 - d1 / d0 if d0 != 0.0 else float("nan")
+        return out
 
     def _cell_result(self, c: Cell, p: Pair, n_gen: int, resp: List[int], probs: np.ndarray, topk_ids: List[int],
                      nll_edit: float, nll_self: float, ro=None) -> dict:

@@ -85,6 +85,10 @@ class Pair:
     # intervention.output_shift only: (the ``resid`` they were computed from, [n, D] final-normed rows of the unedited
     # blocks past the hooked layer over ``resid``) -- the baseline side of the cells' KL (ReadoutMixin._shift_base)
     x_base: Optional[tuple] = None
+    # intervention.layer_trace only: (the ``resid`` they were computed from, [n, Lt, T] fp32 host tensor: the capped lens
+    # logits of ``track`` at blocks l .. layers - 1 of the same unedited pass) -- the baseline side of the cells'
+    # ``trace_*`` fields (ReadoutMixin._shift_base)
+    z_base: Optional[tuple] = None
 
     def ro_order(self) -> List[int]:
         """Column order of ``track`` in the tracking head's id table (output readout): the secret's two forms, the

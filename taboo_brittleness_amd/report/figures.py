@@ -10,6 +10,9 @@
 * ``fig5_collateral.png`` — output shift (``intervention.output_shift``), only for sweeps run with it: the KL between
   the baseline's and the edited next-token distribution vs budget / rank, targeted against its controls; with the
   output readout also the specificity plane (Δ log-prob of the secret against that KL);
+* ``fig6_layer_trace.png`` — layer trace (``intervention.layer_trace``), only for sweeps run with it: the change of the
+  secret's capped lens logit at the edited rows against the block it is read at, one line per budget, targeted
+  against its controls;
 * ``table_baselines.csv`` — LL-Top-k / SAE-Top-k / token forcing rows with
   Pass@10, Majority@10, Accuracy.
 """
@@ -264,6 +267,41 @@ def collateral_curves(summary: Dict, path: str) -> None:
     plt.close(fig)
 
 
+def layer_trace_curves(summary: Dict, path: str) -> None:
+    """Layer trace (intervention.layer_trace): ``trace_dz_spike`` -- the change of the secret's capped logit-lens logit
+    at the edited rows, edited minus baseline -- against the block it is read at, from the hooked layer (where the edit
+    is written) to the last: one line per budget m (SAE methods) or rank r (subspace methods), the targeted method
+    solid against its controls dashed, with 95 % bootstrap intervals.  A line that returns towards 0 is an edit the
+    later blocks repair; the legend carries each line's ``trace_recovery``."""
+    curves = [c for c in summary["curves"] if "trace_dz_spike" in c]
+    blocks = summary.get("config", {}).get("trace_blocks") or list(range(len(curves[0]["trace_dz_spike"])))
+    fig, axes = plt.subplots(1, 2, figsize=(11, 4.2), squeeze=False)
+    for ax, kind in zip(axes[0], ("sae", "proj")):
+        mine = [c for c in curves if c["method"].startswith(kind + "_")]
+        buds = sorted({c["budget"] for c in mine})
+        for c in sorted(mine, key=lambda c: (c["method"], c["budget"])):
+            main = c["method"].endswith("targeted") or c["method"].endswith("_swap")
+            ys = [ci["mean"] for ci in c["trace_dz_spike"]]
+            shade = 0.35 + 0.65 * (buds.index(c["budget"]) + 1) / len(buds)
+            rec = c["trace_recovery"]["mean"]
+            ax.plot(blocks, ys, "o-" if main else "s--", color=_method_colour(c["method"]), alpha=shade, lw=1.2,
+                    ms=3, label=f"{c['method']} {c['budget']}" + (f" (rec {rec:.2f})" if rec == rec else ""))
+            ax.fill_between(blocks, [ci["lo"] for ci in c["trace_dz_spike"]], [ci["hi"] for ci in c["trace_dz_spike"]],
+                            color=_method_colour(c["method"]), alpha=0.08)
+        ax.axhline(0, color="k", lw=0.5)
+        ax.set_xlabel("block")
+        ax.set_ylabel("Δ capped lens logit of the secret at the spikes")
+        ax.set_title(f"layer trace downstream of the edit: {kind}")
+        if ax.get_legend_handles_labels()[0]:
+            ax.legend(fontsize=6, ncol=2)
+    if mode_label(summary):
+        fig.suptitle(f"sae cells: {mode_label(summary)}")
+    plt.tight_layout()
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    fig.savefig(path, dpi=150)
+    plt.close(fig)
+
+
 def baselines_table(rows: Dict[str, Dict[str, float]], path: str) -> None:
     lines = ["method,pass@10,majority@10,accuracy"]
     for name, m in rows.items():
@@ -304,6 +342,10 @@ def make_report(results_dir: str, out_dir: str) -> List[str]:
             if any("kl_out_mean" in c for c in s["curves"]):       # only sweeps run with the output shift
                 p = os.path.join(out_dir, f"fig5_collateral_{tag}.png")
                 collateral_curves(s, p)
+                made.append(p)
+            if any("trace_dz_spike" in c for c in s["curves"]):    # only sweeps run with the layer trace
+                p = os.path.join(out_dir, f"fig6_layer_trace_{tag}.png")
+                layer_trace_curves(s, p)
                 made.append(p)
             if s.get("baselines"):
                 from .dashboards import write_latent_dashboard
