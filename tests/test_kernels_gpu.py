@@ -1014,6 +1014,55 @@ def test_attention_decode_split_bitequal(gpu, G, S):
         k.attention_split_rows(old[1], True)
 
 
+@pytest.mark.parametrize("G,HD", [(2, 256), (1, 128)])
+@pytest.mark.parametrize("Hkv", [1, 2, 6])
+def test_attention_decode_bits_by_kv_heads(gpu, Hkv, G, HD):
+    """The one-wave decode kernel packs 4, 2 or 1 kv heads into a workgroup depending on Hkv (the other bit-equality
+    tests run Hkv = 4 only): at 1, 2 and 6 kv heads its rows equal, bit for bit, the same rows run as packed blocks
+    through the tail kernel and (HD = 256) through the 4-wave split kernel.  S = 48 with rows at positions 0, 15, 16
+    and 47 and a padding row, windows 0 and 17, with and without shared prefixes of 0, 7, 16 and 40 keys: a tile
+    boundary, a window edge and a prefix cut at the smallest shapes that have them."""
+    from taboo_brittleness_amd.models.gemma2 import packed_blocks
+
+    torch.manual_seed(29)
+    S, B = 48, 5
+    Hq = Hkv * G
+    d = lambda t: t.to(gpu)                               # noqa: E731
+    kc = d(torch.randn(B, Hkv, S, HD, dtype=BF))
+    vc = d(torch.randn(B, Hkv, S, HD, dtype=BF))
+    pk = d(torch.randn(2, Hkv, S, HD, dtype=BF))
+    pv = d(torch.randn(2, Hkv, S, HD, dtype=BF))
+    q = d(torch.randn(B, Hq, HD, dtype=BF) * 2)
+    pos = torch.tensor([0, 15, 16, 47, -1], dtype=torch.int32)
+    slot = torch.tensor([3, 0, 4, 1, 2], dtype=torch.int32)
+    ps = torch.tensor([0, 1, 0, 1, 0], dtype=torch.int32)
+    pl = torch.tensor([0, 7, 16, 40, 0], dtype=torch.int32)
+    seqs = [(i, 1, int(slot[i]), int(ps[i]), int(pl[i])) for i in range(B)]
+    k = ops._k()
+    old = k.attention_split_rows(-1, True), k.attention_split_rows(-1, False)
+    try:
+        for window in (0, 17):
+            for prefix in (False, True):
+                blk = d(packed_blocks(seqs if prefix else [s[:3] for s in seqs], 16 // G))
+                tail = ops.attention_varlen(q, kc, vc, d(pos), d(slot), blk, HD ** -0.5, 50.0, window,
+                                            prefix_kv=(pk, pv) if prefix else None)
+                outs = {}
+                for name, split in (("wave", 0), ("split", 1 << 20)):
+                    k.attention_split_rows(split, prefix)
+                    outs[name] = ops.attention(q, kc, vc, d(pos), d(slot), B, 1, HD ** -0.5, 50.0, window,
+                                               prefix=(pk, pv, d(ps), d(pl)) if prefix else None)
+                torch.cuda.synchronize()
+                wave = outs["wave"]
+                assert torch.isfinite(wave.float()).all() and (wave[4] == 0).all() and (tail[4] == 0).all()
+                assert wave[:4].float().abs().sum() > 0
+                assert torch.equal(wave, tail), (window, prefix, (wave.float() - tail.float()).abs().max().item())
+                if HD == 256:      # (at HD = 128 the threshold selects nothing: both runs are the wave kernel)
+                    assert torch.equal(wave, outs["split"]), (window, prefix)
+    finally:
+        k.attention_split_rows(old[0], True)
+        k.attention_split_rows(old[1], False)
+
+
 @pytest.mark.parametrize("G", [2, 4])
 def test_attention_decode_wave_s2048(gpu, G):
     """the one-wave decode kernel near S = 2048 needs more than 64 KB of dynamic LDS (4 kv heads per

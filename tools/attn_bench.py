@@ -5,6 +5,10 @@ the kernel time and two byte rates: "streamed" (every K/V row each wave reads) a
 + every row's own keys: the HBM floor if the prefix is reused through the caches).
 
   python tools/attn_bench.py [--rows 256,1024,2048,4096] [--reps 20]
+
+``--tail`` times the packed tail kernel instead (``ops.attention_varlen``, 5-column block table): the sweep's
+teacher-forced tails, cells of about 30 consecutive rows of one slot starting at positions 17..67, each reading its
+pair's shared prefix up to its first row (default rows 2048,16384).
 """
 from __future__ import annotations
 
@@ -21,9 +25,55 @@ from taboo_brittleness_amd import ops  # noqa: E402
 BF = torch.bfloat16
 
 
+def timed_us(f, reps):
+    for _ in range(3):
+        f()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        f()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps * 1e3
+
+
+def bench_tail(args, dev, g, Hq, Hkv, HD, S):
+    from taboo_brittleness_amd.models.gemma2 import packed_blocks
+
+    n = args.tail_rows
+    assert args.prompt + args.gen + n <= S, "a cell's last row must fit the cache"
+    for M in [int(v) for v in args.rows.split(",")]:
+        ncell = -(-M // n)
+        P = -(-ncell // args.cells)
+        kc = torch.randn(ncell, Hkv, S, HD, device=dev, dtype=BF)
+        vc = torch.randn(ncell, Hkv, S, HD, device=dev, dtype=BF)
+        pk = torch.randn(P, Hkv, S, HD, device=dev, dtype=BF)
+        pv = torch.randn(P, Hkv, S, HD, device=dev, dtype=BF)
+        q = torch.randn(M, Hq, HD, device=dev, dtype=BF)
+        first = args.prompt + torch.randint(0, args.gen + 1, (ncell,), generator=g)     # 17..67
+        seqs, pos, slot_rows = [], [], []
+        for c in range(ncell):
+            rows = min(n, M - c * n)
+            p0 = int(first[c])
+            seqs.append((c * n, rows, c, c // args.cells, p0))      # prefix = the keys before the cell's first row
+            pos += list(range(p0, p0 + rows))
+            slot_rows += [c] * rows
+        blk = packed_blocks(seqs, 16 // (Hq // Hkv)).to(dev)
+        pos_d = torch.tensor(pos, dtype=torch.int32, device=dev)
+        sr_d = torch.tensor(slot_rows, dtype=torch.int32, device=dev)
+        out = torch.empty(M, Hq * HD, device=dev, dtype=BF)
+        us = timed_us(lambda: ops.attention_varlen(q, kc, vc, pos_d, sr_d, blk, HD ** -0.5, 50.0, 0, out=out,
+                                                   prefix_kv=(pk, pv)), args.reps)
+        print(json.dumps({"rows": M, "tail": True, "cells": ncell, "blocks": int(blk.shape[0]), "tail_us": round(us, 1),
+                          "mean_keys": round(float(pos_d.float().mean()) + 1, 1)}), flush=True)
+        del kc, vc, pk, pv, q, out
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--rows", default="256,1024,2048,4096")
+    ap.add_argument("--rows", default=None, help="default 256,1024,2048,4096; with --tail 2048,16384")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--cells", type=int, default=66, help="rows per pair (shared prefix)")
     ap.add_argument("--S", type=int, default=128)
@@ -33,10 +83,16 @@ def main():
     ap.add_argument("--own", action="store_true",
                     help="rows with their own keys only (no shared prefix: the token-forcing decode): one-wave vs "
                          "4-wave kernel")
+    ap.add_argument("--tail", action="store_true", help="packed tail rows through ops.attention_varlen")
+    ap.add_argument("--tail-rows", type=int, default=30, help="--tail: rows per cell")
     args = ap.parse_args()
+    if args.rows is None:
+        args.rows = "2048,16384" if args.tail else "256,1024,2048,4096"
     dev = torch.device("cuda:0")
     Hq, Hkv, HD, S = 16, 8, 256, args.S
     g = torch.Generator(device="cpu").manual_seed(args.seed)
+    if args.tail:
+        return bench_tail(args, dev, g, Hq, Hkv, HD, S)
     for M in [int(v) for v in args.rows.split(",")]:
         P = -(-M // args.cells)
         kc = torch.randn(M, Hkv, S, HD, device=dev, dtype=BF)
@@ -70,16 +126,7 @@ def main():
             variants = {"wave": lambda: _plain(0), "split": lambda: _plain(1 << 20)}
         res = {}
         for name, f in variants.items():
-            for _ in range(3):
-                f()
-            torch.cuda.synchronize()
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(args.reps):
-                f()
-            b.record()
-            torch.cuda.synchronize()
-            res[name] = a.elapsed_time(b) / args.reps * 1e3
+            res[name] = timed_us(f, args.reps)
         kx.attention_split_rows(old_split[0], False)
         kx.attention_split_rows(old_split[1], True)
         us = res["wave"]
