@@ -38,8 +38,14 @@ def main(argv=None):
                     help="also record the capped lens logit of the tracked ids at every block from the hooked layer on, "
                          "for each cell and its baseline over the teacher-forced response (intervention.layer_trace; "
                          "needs layer resume; no TP or decode-tail carry-over)")
+    ap.add_argument("--output-movers", action="store_true",
+                    help="also record, per edited spike, the tokens that gained and lost the most next-token "
+                         "probability against the baseline and the total variation (intervention.output_movers, "
+                         "intervention.movers_k; needs layer resume; no fused head, TP or decode-tail carry-over)")
     args = ap.parse_args(argv)
     cfg, dev = setup(args)
+    if args.output_movers:
+        cfg.intervention.output_movers = True
     if args.layer_trace:
         cfg.intervention.layer_trace = True
     if args.forcing:

@@ -161,6 +161,14 @@ class InterventionCfg:
     # packed pass); adds the ``trace_*`` record fields, curves, sweep_trace.csv and fig6_layer_trace.  Needs layer
     # resume; off: records, files and launched kernels are what they are without it.
     layer_trace: bool = False
+    # output movers (opt-in): where the probability went -- per edited spike the ``movers_k`` tokens that gained and
+    # that lost the most next-token probability against the baseline's row, and the total variation between the two
+    # distributions (ops.head_movers over the tail's rows right behind a spike and the baseline's rows); adds the
+    # ``movers_*`` / ``tv_out_spike_mean`` / ``secret_loss_share`` / ``*_in_gainers`` / ``top_gainer`` record fields,
+    # curves, movers_top.csv and fig7_movers.  Needs layer resume; off: records, files and launched kernels are what
+    # they are without it.
+    output_movers: bool = False
+    movers_k: int = 8                   # list length per spike, 1..8 (the kernel's register lists)
     score_over: str = "prompt"          # "prompt" (per prompt) or "word" (average over prompts)
     # how the targeted latents are ranked: "corr" (EP:118-124: spike-mean activation x positive correlation with the
     # secret probability), or by what ablating the latent alone does at the spikes: "effect_lens" (the exact drop of

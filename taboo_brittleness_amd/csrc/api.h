@@ -73,6 +73,14 @@ int tb_decode_head_track(const uint16_t* logits, const int32_t* tgt, int32_t* nx
 // Return codes as tb_decode_head_track (3 = V < 1).
 int tb_head_shift(const uint16_t* logits, const uint16_t* base, const int32_t* rowmap, float* kl, float* kl_rev, int R,
                   int Rb, int V, float cap, hipStream_t st);
+// output movers: for selected row i with r = rows[i] ([Rs] int32) and b = rowmap[r], d = softmax c(logits[r]) -
+// softmax c(base[b]): tv[i] = 1/2 sum |d|, up_id / up_dp [Rs, K] the K largest d > 0 (d descending, id ascending),
+// dn_id / dn_dp [Rs, K] the K smallest d < 0 (d ascending, id ascending), unfilled slots -1 / +0.0, dp_track [Rs, T] =
+// d at ids [Rs, T] (0 for an id outside [0, V)).  rows[i] outside [0, R) or rowmap[r] outside [0, Rb) writes zeros and
+// empty lists.  Return codes as tb_decode_head_track (3 = V < 1, K outside [1, 8] or T outside [0, 8]).
+int tb_head_movers(const uint16_t* logits, const uint16_t* base, const int32_t* rowmap, const int32_t* rows,
+                   const int32_t* ids, int T, int K, float* tv, int32_t* up_id, float* up_dp, int32_t* dn_id,
+                   float* dn_dp, float* dp_track, int R, int Rb, int Rs, int V, float cap, hipStream_t st);
 // sae.hip
 void tb_head_merge(const float* part, int npart, const int32_t* tgt, const float* tgt_logit, int32_t* nxt,
                    float* nll_self, float* nll_tgt, float* lse, int M, int V, hipStream_t st);

@@ -455,6 +455,46 @@ void head_shift(torch::Tensor logits, torch::Tensor base, torch::Tensor rowmap, 
   TORCH_CHECK(rc == 0, "head_shift: bad arguments");
 }
 
+// output movers (lens.hip head_movers_kernel): logits [R, V], base [Rb, V] bf16, rowmap [R], rows [Rs] int32, ids
+// [Rs, T] int32 (optional) -> tv [Rs] f32, up_id / dn_id [Rs, k] i32, up_dp / dn_dp [Rs, k] f32, dp_track [Rs, T] f32
+void head_movers(torch::Tensor logits, torch::Tensor base, torch::Tensor rowmap, torch::Tensor rows,
+                 c10::optional<torch::Tensor> ids, int64_t k, torch::Tensor tv, torch::Tensor up_id, torch::Tensor up_dp,
+                 torch::Tensor dn_id, torch::Tensor dn_dp, torch::Tensor dp_track, double cap) {
+  IN_BF16(logits); IN_BF16(base); IN_I32(rowmap); IN_I32(rows); IN_F32(tv); IN_I32(up_id); IN_F32(up_dp); IN_I32(dn_id);
+  IN_F32(dn_dp); IN_F32(dp_track);
+  TORCH_CHECK(logits.dim() == 2 && base.dim() == 2 && base.size(1) == logits.size(1),
+              "head_movers: logits [R, V] and base [Rb, V] must share V");
+  const int64_t V = logits.size(1), R = logits.size(0), Rb = base.size(0), Rs = rows.numel();
+  TORCH_CHECK(V >= 1 && R < (1LL << 31) && Rb < (1LL << 31) && V < (1LL << 31) && Rs < (1LL << 31), "head_movers: sizes");
+  TORCH_CHECK(k >= 1 && k <= 8, "head_movers: 1 <= k <= 8 list entries, got ", k);
+  int64_t T = 0;
+  const int32_t* ip = nullptr;
+  if (ids.has_value()) {
+    IN_I32((*ids));
+    TORCH_CHECK(ids->dim() == 2 && ids->size(0) == Rs, "head_movers: ids must be [Rs, T]");
+    T = ids->size(1);
+    TORCH_CHECK(T <= 8, "head_movers: T <= 8 tracked ids, got ", T);
+    TORCH_CHECK(ids->device() == logits.device(), "head_movers: one device");
+    if (T > 0) ip = ids->data_ptr<int32_t>();
+  }
+  TORCH_CHECK(rowmap.numel() == R && tv.numel() == Rs, "head_movers: rowmap must be [R], tv [Rs]");
+  TORCH_CHECK(up_id.numel() == Rs * k && up_dp.numel() == Rs * k && dn_id.numel() == Rs * k && dn_dp.numel() == Rs * k,
+              "head_movers: the lists must be [Rs, k]");
+  TORCH_CHECK(dp_track.numel() == Rs * T, "head_movers: dp_track must be [Rs, T]");
+  for (const torch::Tensor* t : {&base, &rowmap, &rows, &tv, &up_id, &up_dp, &dn_id, &dn_dp, &dp_track})
+    TORCH_CHECK(t->device() == logits.device(), "head_movers: one device");
+  TORCH_CHECK(cap > 0, "head_movers needs a final softcap (0 < cap <= 40), got ", cap);
+  c10::DeviceGuard g(logits.device());
+  const int rc = tb_head_movers(cbf(logits), cbf(base), rowmap.data_ptr<int32_t>(), rows.data_ptr<int32_t>(), ip, (int)T,
+                                (int)k, tv.data_ptr<float>(), up_id.data_ptr<int32_t>(), up_dp.data_ptr<float>(),
+                                dn_id.data_ptr<int32_t>(), dn_dp.data_ptr<float>(), dp_track.data_ptr<float>(), (int)R,
+                                (int)Rb, (int)Rs, (int)V, (float)cap, cur_stream());
+  TORCH_CHECK(rc != 1, "head_movers: cap ", cap, " has no registered softcap table or exceeds 40 (the kernel exists for "
+              "the default decode_head kernel only)");
+  TORCH_CHECK(rc != 2, "head_movers: TB_DECODE_HEAD selects the t / c kernel, which has no movers version");
+  TORCH_CHECK(rc == 0, "head_movers: bad arguments");
+}
+
 // vocab-parallel decode head (this rank's V columns of the logits): float4 stats per row for vp_head_merge; returns
 // false (nothing launched) when the cap has no registered softcap table
 bool decode_head_stats(torch::Tensor logits, c10::optional<torch::Tensor> tgt, int64_t off, torch::Tensor stats,
@@ -1315,6 +1355,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_head_stats", &decode_head_stats);
   m.def("decode_head_track", &decode_head_track);
   m.def("head_shift", &head_shift);
+  m.def("head_movers", &head_movers);
   m.def("register_softcap_table", &register_softcap_table);
   m.def("register_softcap_compact", &register_softcap_compact);
   m.def("softcap_compact", &softcap_compact);

@@ -18,6 +18,8 @@
 //                 output-side readout), counted in the same streamed pass
 //  head_shift     KL(base || edit) and KL(edit || base) of an edited logits row against its baseline row (the
 //                 sweep's output-shift readout), one streamed pass over both rows
+//  head_movers    total variation between the two distributions of selected rows and the k tokens that gained /
+//                 lost the most probability (the sweep's output-movers readout), two streamed passes
 #include "common.h"
 #include "api.h"
 #include <algorithm>
@@ -893,6 +895,270 @@ __global__ void __launch_bounds__(512) head_shift_kernel(const uint16_t* __restr
   }
 }
 
+// Output movers of an edit: where the probability went.  For selected row i with r = rows[i], b = rowmap[r],
+// q = c(logits[r]) and p = c(base[b]) (head_shift_kernel's capped values, through the same LDS table):
+//   pass 1   S_p = sum e^p, S_q = sum e^q -- head_shift_kernel's two sums, statement for statement
+//   thread 0 rp = 1 / S_p, rq = 1 / S_q, handed to the block through LDS
+//   pass 2   d_v = fl(e^{q_v} rq) - fl(e^{p_v} rp) per column (never contracted into an fma), tv = 1/2 sum |d_v|,
+//            and per wave the K best gainers (d > 0) and the K best losers (d < 0) in sorted lists across its lanes
+//   a merge of the eight waves' lists gives up_id / up_dp (d descending, id ascending) and dn_id / dn_dp (d
+//   ascending, id ascending; the negative value); unfilled slots hold -1 and +0.0
+//   dp_track[i, t] = d at column ids[i, t], through the statements its column takes in pass 2 (movers_d2 in the
+//   16-B body, movers_d1 in the V % 8 tail): an id that is also listed carries the same float there.  An id outside
+//   [0, V) gives 0.
+// rows[i] outside [0, R) or rowmap[r] outside [0, Rb) writes 0, empty lists and zeros and reads neither row.
+// Bits: d_v is a pure function of (p_v, q_v, rp, rq) and of whether column v lies in the body or the tail, which V
+// alone decides; S_p, S_q and tv add per lane in index order over c = tid, tid + 512, ..., then the tail, the wave
+// butterfly and the waves in order, as head_shift_kernel's sums do; the lists' order (value, then id) is total, so
+// neither the traversal nor the merge order can show.  A row's outputs are a function of V, K, ids[i] and the two
+// rows' bits.  Identical rows: S_p and S_q are the same float, so are rp and rq and every product, every d is +0
+// and so is tv; no d > 0 or d < 0 exists, so both lists stay empty.
+// The losers' list keeps -d, so one ordering serves both lists; an empty entry is (0, -1), below every real one.
+constexpr int HM_KMAX = 8;    // list length (ops.HEAD_MOVERS_KMAX)
+constexpr int HM_TMAX = 8;    // tracked ids per row
+
+__device__ __forceinline__ f2 movers_d2(f2 P, f2 Q, float rp, float rq) {
+#pragma clang fp contract(off)
+  const f2 yp = P * LOG2E2, yq = Q * LOG2E2;
+  const f2 ep = {__builtin_amdgcn_exp2f(yp.x), __builtin_amdgcn_exp2f(yp.y)};
+  const f2 eq = {__builtin_amdgcn_exp2f(yq.x), __builtin_amdgcn_exp2f(yq.y)};
+  const f2 a = eq * f2{rq, rq};
+  const f2 b = ep * f2{rp, rp};
+  return a - b;
+}
+__device__ __forceinline__ float movers_d1(float p, float q, float rp, float rq) {
+#pragma clang fp contract(off)
+  const float a = __expf(q) * rq;
+  const float b = __expf(p) * rp;
+  return a - b;
+}
+
+// A wave's K best (value, column) pairs, entry j in lane j, sorted (value descending, column ascending); lanes from K
+// on hold the empty pair (0, -1), which is below every real one.  The K-th pair is the wave's threshold, kept
+// wave-uniform, so the common case costs one compare per column and the rare entry runs once for the whole wave (a
+// list per lane made nearly every column a slow one: some lane of the 64 almost always had something to insert).
+// offer() takes one candidate per lane and inserts those that pass, lane by lane: the position is the number of
+// entries that stay ahead, the entries behind it move down one lane.
+struct WaveList {
+  float v;
+  int i;
+  float thv;
+  int thi;
+  __device__ __forceinline__ void clear() {
+    v = 0.f;
+    i = -1;
+    thv = 0.f;
+    thi = -1;
+  }
+  __device__ __forceinline__ void offer(float x, int c, int K) {
+    const int lane = threadIdx.x & 63;
+    unsigned long long m = __builtin_amdgcn_ballot_w64(x > thv || (x == thv && c < thi));   // x <= 0 never passes
+    while (m != 0) {   // wave-uniform
+      const int src = __builtin_ctzll(m);
+      m &= m - 1;
+      const float xs = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), src));
+      const int cs = __builtin_amdgcn_readlane(c, src);
+      if (!(xs > thv || (xs == thv && cs < thi))) continue;   // the threshold has risen since the ballot
+      const bool ahead = lane < K && (v > xs || (v == xs && i < cs));
+      const int pos = __builtin_popcountll(__builtin_amdgcn_ballot_w64(ahead));
+      const float vu = __shfl_up(v, 1, 64);
+      const int iu = __shfl_up(i, 1, 64);
+      if (lane >= K) { v = 0.f; i = -1; }
+      else if (lane > pos) { v = vu; i = iu; }
+      else if (lane == pos) { v = xs; i = cs; }
+      thv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), K - 1));
+      thi = __builtin_amdgcn_readlane(i, K - 1);
+    }
+  }
+};
+
+struct HeadMovers {
+  const int32_t* rowmap;   // [R]
+  const int32_t* rows;     // [Rs]
+  const int32_t* ids;      // [Rs, T] or nullptr (T = 0)
+  float* tv;               // [Rs]
+  int32_t* up_id;          // [Rs, K]
+  float* up_dp;
+  int32_t* dn_id;
+  float* dn_dp;
+  float* dp_track;         // [Rs, T]
+  int R, Rb, Rs, V, K, T;
+};
+
+template <int UNR>
+__global__ void __launch_bounds__(512) head_movers_kernel(const uint16_t* __restrict__ logits,
+                                                          const uint16_t* __restrict__ base,
+                                                          const uint16_t* __restrict__ tab, HeadMovers hm) {
+  __shared__ Slots<float> sh[3];
+  __shared__ float srec[2];
+  __shared__ float lv[2][8][HM_KMAX];   // the waves' lists: [up / dn][wave][entry]
+  __shared__ int li[2][8][HM_KMAX];
+  extern __shared__ __attribute__((aligned(16))) uint16_t ctab_lds[];
+  const uint16_t* ct = stage_ctab(tab, ctab_lds);
+  const int V = hm.V, K = hm.K, T = hm.T;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int nv = V >> 3;
+  for (int i = blockIdx.x; i < hm.Rs; i += gridDim.x) {
+    const int r = hm.rows[i];
+    const int b = (r >= 0 && r < hm.R) ? hm.rowmap[r] : -1;
+    if (b < 0 || b >= hm.Rb) {   // block-uniform
+      if (threadIdx.x == 0) {
+        hm.tv[i] = 0.f;
+        for (int k = 0; k < K; ++k) {
+          hm.up_id[(size_t)i * K + k] = -1;
+          hm.up_dp[(size_t)i * K + k] = 0.f;
+          hm.dn_id[(size_t)i * K + k] = -1;
+          hm.dn_dp[(size_t)i * K + k] = 0.f;
+        }
+        for (int t = 0; t < T; ++t) hm.dp_track[(size_t)i * T + t] = 0.f;
+      }
+      continue;
+    }
+    const uint16_t* rq_ = logits + (size_t)r * V;
+    const uint16_t* rp_ = base + (size_t)b * V;
+    const uint4* pp = reinterpret_cast<const uint4*>(rp_);
+    const uint4* pq = reinterpret_cast<const uint4*>(rq_);
+    const int st = blockDim.x;
+    // ---- pass 1: the two exp-sums (head_shift_kernel's statements for sp2 / sq2, sp / sq)
+    f2 sp2 = {0.f, 0.f}, sq2 = {0.f, 0.f};
+    auto sum8 = [&](const uint4& vp, const uint4& vq) {
+      float p[8], q[8];
+      capped8_tab(vp, p, ct);
+      capped8_tab(vq, q, ct);
+#pragma unroll
+      for (int j = 0; j < 8; j += 2) {
+        const f2 P = {p[j], p[j + 1]}, Q = {q[j], q[j + 1]};
+        const f2 yp = P * LOG2E2, yq = Q * LOG2E2;
+        const f2 ep = {__builtin_amdgcn_exp2f(yp.x), __builtin_amdgcn_exp2f(yp.y)};
+        const f2 eq = {__builtin_amdgcn_exp2f(yq.x), __builtin_amdgcn_exp2f(yq.y)};
+        sp2 += ep;
+        sq2 += eq;
+      }
+    };
+    {
+      int c = threadIdx.x;
+      for (; c + (UNR - 1) * st < nv; c += UNR * st) {   // 2 UNR loads in flight per lane
+        uint4 vp[UNR], vq[UNR];
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) { vp[u] = pp[c + u * st]; vq[u] = pq[c + u * st]; }
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) sum8(vp[u], vq[u]);
+      }
+      for (; c < nv; c += st) sum8(pp[c], pq[c]);
+    }
+    float sp = sp2.x + sp2.y, sq = sq2.x + sq2.y;
+    for (int c = nv * 8 + threadIdx.x; c < V; c += blockDim.x) {
+      const float p = capped1(rp_[c], ct, 0.f, 1), q = capped1(rq_[c], ct, 0.f, 1);
+      sp += __expf(p);
+      sq += __expf(q);
+    }
+    block_reduce(red(sp, sh[0]), red(sq, sh[1]));
+    if (threadIdx.x == 0) {
+      srec[0] = 1.0f / sp;
+      srec[1] = 1.0f / sq;
+    }
+    __syncthreads();
+    const float rp = srec[0], rq = srec[1];
+    // ---- the tracked ids, one thread each
+    if ((int)threadIdx.x < T) {
+      const int id = hm.ids[(size_t)i * T + threadIdx.x];
+      float d = 0.f;
+      if (id >= 0 && id < V) {
+        const float p = capped1(rp_[id], ct, 0.f, 1), q = capped1(rq_[id], ct, 0.f, 1);
+        d = id < nv * 8 ? movers_d2(f2{p, p}, f2{q, q}, rp, rq).x : movers_d1(p, q, rp, rq);
+      }
+      hm.dp_track[(size_t)i * T + threadIdx.x] = d;
+    }
+    // ---- pass 2: the differences, their absolute sum and the wave's candidates.  The lists live across the lanes of a
+    // wave, so every trip is run by whole waves: a lane past the row's end takes part with zeros, which add +0 to its
+    // sum (no bit changes) and are never offered
+    WaveList up, dn;
+    up.clear();
+    dn.clear();
+    f2 t2 = {0.f, 0.f};
+    auto diff8 = [&](const uint4& vp, const uint4& vq, int c, bool ok) {
+      float p[8], q[8], d[8];
+      capped8_tab(vp, p, ct);
+      capped8_tab(vq, q, ct);
+#pragma unroll
+      for (int j = 0; j < 8; j += 2) {
+        const f2 dd = movers_d2(f2{p[j], p[j + 1]}, f2{q[j], q[j + 1]}, rp, rq);
+        d[j] = ok ? dd.x : 0.f;
+        d[j + 1] = ok ? dd.y : 0.f;
+        t2 += f2{fabsf(d[j]), fabsf(d[j + 1])};
+      }
+      // one test per list and vector: nothing below the wave's threshold can enter (offer decides exactly)
+      const float mx = fmaxf(fmaxf(fmaxf(d[0], d[1]), fmaxf(d[2], d[3])), fmaxf(fmaxf(d[4], d[5]), fmaxf(d[6], d[7])));
+      const float mn = fminf(fminf(fminf(d[0], d[1]), fminf(d[2], d[3])), fminf(fminf(d[4], d[5]), fminf(d[6], d[7])));
+      if (__builtin_amdgcn_ballot_w64(mx > 0.f && mx >= up.thv) != 0) {   // wave-uniform
+#pragma unroll
+        for (int j = 0; j < 8; ++j) up.offer(d[j], c * 8 + j, K);
+      }
+      if (__builtin_amdgcn_ballot_w64(mn < 0.f && -mn >= dn.thv) != 0) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) dn.offer(-d[j], c * 8 + j, K);
+      }
+    };
+    {
+      // per lane the order of the plain loop (c = tid, tid + 512, ...); the trip counts are the wave's: UNR-deep while
+      // the wave's last lane has all UNR vectors, then one vector at a time while its first lane has one
+      int c = threadIdx.x;
+      int cw = __builtin_amdgcn_readfirstlane(threadIdx.x) + 63;
+      for (; cw + (UNR - 1) * st < nv; cw += UNR * st, c += UNR * st) {
+        uint4 vp[UNR], vq[UNR];
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) { vp[u] = pp[c + u * st]; vq[u] = pq[c + u * st]; }
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) diff8(vp[u], vq[u], c + u * st, true);
+      }
+      for (; cw - 63 < nv; cw += st, c += st) {
+        const bool ok = c < nv;
+        const uint4 z = {0u, 0u, 0u, 0u};
+        diff8(ok ? pp[c] : z, ok ? pq[c] : z, c, ok);
+      }
+    }
+    float ts = t2.x + t2.y;
+    if (wid == 0) {   // the V % 8 tail: at most 7 columns, lanes 0..6 of wave 0 (the plain loop's lanes), as a whole wave
+      const int c = nv * 8 + lane;
+      const bool ok = c < V;
+      const float d = ok ? movers_d1(capped1(rp_[ok ? c : 0], ct, 0.f, 1), capped1(rq_[ok ? c : 0], ct, 0.f, 1), rp, rq)
+                         : 0.f;
+      ts += fabsf(d);
+      up.offer(d, c, K);
+      dn.offer(-d, c, K);
+    }
+    if (lane < HM_KMAX) {   // lanes from K on hold the empty pair
+      lv[0][wid][lane] = up.v;
+      li[0][wid][lane] = up.i;
+      lv[1][wid][lane] = dn.v;
+      li[1][wid][lane] = dn.i;
+    }
+    block_reduce(red(ts, sh[2]));   // its barrier publishes the waves' lists as well
+    if (threadIdx.x == 0) hm.tv[i] = 0.5f * ts;
+    // ---- wave 0 merges the waves' sorted lists: lane w holds the head of wave w's list, K rounds of arg-best over the
+    // heads, the winning lane moves on to its next entry
+    if (wid == 0) {
+      const int nw = blockDim.x >> 6;
+      int hu = 0, hd = 0;
+      for (int k = 0; k < K; ++k) {
+        const ArgBest mu = (lane < nw && hu < K) ? ArgBest{lv[0][lane][hu], li[0][lane][hu]} : ArgBest{0.f, -1};
+        const ArgBest md = (lane < nw && hd < K) ? ArgBest{lv[1][lane][hd], li[1][lane][hd]} : ArgBest{0.f, -1};
+        ArgBest bu = mu, bd = md;
+        wave_reduce(bu, bd);
+        if (lane == 0) {
+          hm.up_id[(size_t)i * K + k] = bu.i;
+          hm.up_dp[(size_t)i * K + k] = bu.v;
+          hm.dn_id[(size_t)i * K + k] = bd.i;
+          hm.dn_dp[(size_t)i * K + k] = bd.v > 0.f ? -bd.v : 0.f;
+        }
+        if (bu.i >= 0 && mu.i == bu.i) ++hu;
+        if (bd.i >= 0 && md.i == bd.i) ++hd;
+      }
+    }
+    __syncthreads();   // the slots, srec and the lists are rewritten by the next row
+  }
+}
+
 // elementwise exact softcap through the compact path (ops.softcap_values; the exhaustive GPU test)
 __global__ void softcap_c_kernel(const uint16_t* __restrict__ x, float* __restrict__ y, int n, CapC cc) {
   __shared__ uint16_t lt[CAPC_MAX];
@@ -1069,6 +1335,22 @@ int tb_head_shift(const uint16_t* logits, const uint16_t* base, const int32_t* r
   if (R <= 0) return 0;
   launch_rows<head_shift_kernel<2>>(std::min(R, 2 * cu_count()), tab, st, logits, base, rowmap, kl, kl_rev, R, Rb, V,
                                     tab);
+  return 0;
+}
+
+// Total variation, top-K gainers / losers and tracked differences of the selected rows (head_movers_kernel).  Only
+// where tb_decode_head runs the f kernel: returns 1 without a registered table or for a cap outside (0,
+// DH_FIXED_CAP], 2 under TB_DECODE_HEAD=t / c, 3 for V < 1, R or Rb < 0, K outside [1, 8] or T outside [0, 8]
+// (nothing launched); 0 on success.
+int tb_head_movers(const uint16_t* logits, const uint16_t* base, const int32_t* rowmap, const int32_t* rows,
+                   const int32_t* ids, int T, int K, float* tv, int32_t* up_id, float* up_dp, int32_t* dn_id,
+                   float* dn_dp, float* dp_track, int R, int Rb, int Rs, int V, float cap, hipStream_t st) {
+  if (V < 1 || R < 0 || Rb < 0 || K < 1 || K > HM_KMAX || T < 0 || T > HM_TMAX || (T > 0 && ids == nullptr)) return 3;
+  const uint16_t* tab;
+  if (const int rc = fixed_path(cap, &tab); rc != 0) return rc;
+  if (Rs <= 0) return 0;
+  const HeadMovers hm{rowmap, rows, ids, tv, up_id, up_dp, dn_id, dn_dp, dp_track, R, Rb, Rs, V, K, T};
+  launch_rows<head_movers_kernel<2>>(std::min(Rs, 2 * cu_count()), tab, st, logits, base, tab, hm);
   return 0;
 }
 

@@ -668,6 +668,70 @@ def head_shift(logits, base, rowmap, cap, kl=None, kl_rev=None):
     return kl, kl_rev
 
 
+HEAD_MOVERS_KMAX = 8    # list entries of head_movers (csrc/lens.hip HM_KMAX); its tracked ids: HEAD_TRACK_MAX
+
+
+def head_movers(logits, base, rowmap, rows, cap, k, ids=None, tv=None, up_id=None, up_dp=None, dn_id=None, dn_dp=None,
+                dp_track=None):
+    """Output movers of edited logits rows: where the probability went.  For selected row ``i`` with ``r = rows[i]``
+    (``[Rs]`` int32, into ``logits [R, V]`` bf16) and ``b = rowmap[r]`` (``[R]`` int32, the map :func:`head_shift`
+    takes, into ``base [Rb, V]`` bf16), ``d = Q - P`` is the difference of the two next-token distributions of the
+    rows' capped logits.  Returns ``(tv, up_id, up_dp, dn_id, dn_dp, dp_track)``: ``tv [Rs] = 1/2 sum |d|`` (the total
+    variation), ``up_id / up_dp [Rs, k]`` the ``k`` columns with the largest ``d > 0`` (``d`` descending, id
+    ascending), ``dn_id / dn_dp [Rs, k]`` the ``k`` with the smallest ``d < 0`` (``d`` ascending, id ascending; the
+    negative value), unfilled slots ``-1`` / ``+0.0``, and ``dp_track [Rs, T] = d`` at ``ids [Rs, T]`` (int32, ``T <=
+    8``; an id outside ``[0, V)`` gives 0; ``[Rs, 0]`` without ``ids``).  ``rows[i]`` outside ``[0, R)`` or
+    ``rowmap[r]`` outside ``[0, Rb)`` gives 0, empty lists and zeros; so do rows of identical bits, exactly; a row's
+    result does not depend on the other rows of the call, and a tracked id that is also listed carries the list's
+    float.  ``1 <= k <= 8``.  The GPU path is one HIP kernel (csrc/lens.hip head_movers_kernel) and exists for the
+    default head kernel only (``0 < cap <= 40``, ``TB_DECODE_HEAD`` unset or ``f``); anything else raises."""
+    if logits.dim() != 2 or base.dim() != 2 or base.shape[1] != logits.shape[1]:
+        raise ValueError(f"head_movers: logits [R, V] and base [Rb, V] must share V, got {tuple(logits.shape)} and "
+                         f"{tuple(base.shape)}")
+    R, V = logits.shape
+    if V < 1:
+        raise ValueError("head_movers: empty rows")
+    if logits.dtype != BF16 or base.dtype != BF16:
+        raise ValueError(f"head_movers: logits and base must be bf16, got {logits.dtype} and {base.dtype}")
+    if rowmap.dtype != torch.int32 or rowmap.dim() != 1 or rowmap.shape[0] != R:
+        raise ValueError(f"head_movers: rowmap must be [R={R}] int32, got {tuple(rowmap.shape)} {rowmap.dtype}")
+    if rows.dtype != torch.int32 or rows.dim() != 1:
+        raise ValueError(f"head_movers: rows must be [Rs] int32, got {tuple(rows.shape)} {rows.dtype}")
+    Rs = rows.shape[0]
+    k = int(k)
+    if not 1 <= k <= HEAD_MOVERS_KMAX:
+        raise ValueError(f"head_movers: 1 <= k <= {HEAD_MOVERS_KMAX} list entries, got {k}")
+    T = 0
+    if ids is not None:
+        if ids.dtype != torch.int32 or ids.dim() != 2 or ids.shape[0] != Rs:
+            raise ValueError(f"head_movers: ids must be [Rs={Rs}, T] int32, got {tuple(ids.shape)} {ids.dtype}")
+        T = ids.shape[1]
+        if T > HEAD_TRACK_MAX:
+            raise ValueError(f"head_movers: T <= {HEAD_TRACK_MAX} tracked ids, got {T}")
+    dev = logits.device
+    if base.device != dev or rowmap.device != dev or rows.device != dev or (ids is not None and ids.device != dev):
+        raise ValueError("head_movers: logits, base, rowmap, rows and ids must be on one device")
+    if logits.is_cuda and not 0 < cap <= 40:
+        raise ValueError(f"head_movers needs a final softcap 0 < cap <= 40 on the GPU, got {cap}")
+    spec = (("tv", tv, (Rs,), torch.float32), ("up_id", up_id, (Rs, k), torch.int32),
+            ("up_dp", up_dp, (Rs, k), torch.float32), ("dn_id", dn_id, (Rs, k), torch.int32),
+            ("dn_dp", dn_dp, (Rs, k), torch.float32), ("dp_track", dp_track, (Rs, T), torch.float32))
+    outs = []
+    for name, o, shape, dt in spec:
+        if o is not None and (tuple(o.shape) != shape or o.dtype != dt or o.device != dev or not o.is_contiguous()):
+            raise ValueError(f"head_movers: {name} must be a contiguous {list(shape)} {dt} tensor on the logits' "
+                             f"device")
+        outs.append(o if o is not None else torch.empty(shape, dtype=dt, device=dev))
+    if logits.is_cuda:
+        _softcap_table(cap, dev)
+        _k().head_movers(logits.contiguous(), base.contiguous(), rowmap, rows.contiguous(),
+                         None if ids is None else ids.contiguous(), k, *outs, float(cap))
+        return tuple(outs)
+    for o, v in zip(outs, ref.head_movers(logits, base, rowmap, rows, cap, k, ids)):
+        o.copy_(v)
+    return tuple(outs)
+
+
 def slot_copy(dst: torch.Tensor, src: torch.Tensor, dst_slots, src_slots, layers: Optional[range] = None,
               src_layers: Optional[range] = None) -> None:
     """``dst[l, dst_slots[i]] = src[l', src_slots[i]]`` for the layer ranges ``layers`` (of dst) and ``src_layers``

@@ -321,6 +321,56 @@ def head_shift(logits: torch.Tensor, base: torch.Tensor, rowmap: torch.Tensor, c
     return torch.where(ok, kl, zero), torch.where(ok, kl_rev, zero)
 
 
+def head_movers(logits: torch.Tensor, base: torch.Tensor, rowmap: torch.Tensor, rows: torch.Tensor, cap: float, k: int,
+                ids: Optional[torch.Tensor] = None):
+    """Output movers of the selected rows ``rows [Rs]`` of ``logits [R, V]`` against ``base[rowmap[r]]`` on the capped
+    values :func:`head_shift` uses: with ``d = softmax q - softmax p`` (``q = c(logits[r])``, ``p = c(base[b])``),
+    ``tv [Rs] = 1/2 sum |d|``, ``up_id / up_dp [Rs, k]`` the ``k`` columns with the largest ``d > 0`` (``d``
+    descending, id ascending), ``dn_id / dn_dp [Rs, k]`` those with the smallest ``d < 0`` (``d`` ascending, id
+    ascending), unfilled slots ``-1`` / ``+0.0``, and ``dp_track [Rs, T] = d`` at ``ids [Rs, T]`` (0 for an id outside
+    ``[0, V)``).  ``rows[i]`` outside ``[0, R)`` or ``rowmap[r]`` outside ``[0, Rb)`` gives zeros and empty lists;
+    identical rows give exactly that too."""
+    R, V = logits.shape
+    Rb = base.shape[0]
+    dev = logits.device
+    rs = rows.reshape(-1).long()
+    Rs = rs.numel()
+    T = 0 if ids is None else ids.shape[1]
+    rok = (rs >= 0) & (rs < R)
+    if R > 0:
+        bm = rowmap.reshape(-1).long()[rs.clamp(0, R - 1)]
+    else:
+        bm = torch.full_like(rs, -1)
+    ok = rok & (bm >= 0) & (bm < Rb)
+    tv = torch.zeros(Rs, dtype=torch.float32, device=dev)
+    up_id = torch.full((Rs, k), -1, dtype=torch.int32, device=dev)
+    dn_id = torch.full((Rs, k), -1, dtype=torch.int32, device=dev)
+    up_dp = torch.zeros(Rs, k, dtype=torch.float32, device=dev)
+    dn_dp = torch.zeros(Rs, k, dtype=torch.float32, device=dev)
+    dp_track = torch.zeros(Rs, T, dtype=torch.float32, device=dev)
+    sel = ok.nonzero().reshape(-1)
+    if sel.numel() == 0:
+        return tv, up_id, up_dp, dn_id, dn_dp, dp_track
+    q = _capped(logits[rs[sel]], cap, True)
+    p = _capped(base[bm[sel]], cap, True)
+    d = torch.softmax(q, -1) - torch.softmax(p, -1)
+    tv[sel] = 0.5 * d.abs().sum(-1)
+    kk = min(k, V)
+    for sign, oi, ov in ((1.0, up_id, up_dp), (-1.0, dn_id, dn_dp)):
+        vals, idx = torch.sort(sign * d, dim=-1, descending=True, stable=True)    # ties: the lower id first
+        vals, idx = vals[:, :kk], idx[:, :kk].to(torch.int32)
+        hit = vals > 0
+        zero = torch.zeros_like(vals)
+        oi[sel, :kk] = torch.where(hit, idx, torch.full_like(idx, -1))
+        ov[sel, :kk] = torch.where(hit, sign * vals, zero)
+    if T:
+        t = ids.reshape(Rs, T).long()[sel]
+        inb = (t >= 0) & (t < V)
+        g = torch.gather(d, 1, t.clamp(0, V - 1))
+        dp_track[sel] = torch.where(inb, g, torch.zeros_like(g))
+    return tv, up_id, up_dp, dn_id, dn_dp, dp_track
+
+
 def gemm_nt(A: torch.Tensor, W: torch.Tensor, epi: int, bias: Optional[torch.Tensor] = None,
             thr: Optional[torch.Tensor] = None) -> torch.Tensor:
     K = A.shape[-1]

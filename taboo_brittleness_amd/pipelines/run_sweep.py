@@ -51,6 +51,9 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
         raise ValueError("intervention.output_readout has no tensor-parallel version (parallel.tp > 1): run it with tp = 1")
     if cfg.intervention.output_shift and cfg.parallel.tp > 1:
         raise ValueError("intervention.output_shift has no tensor-parallel version (parallel.tp > 1): run it with tp = 1")
+    if cfg.intervention.output_movers and cfg.parallel.tp > 1:
+        raise ValueError("intervention.output_movers has no tensor-parallel version (parallel.tp > 1): run it with "
+                         "tp = 1")
     if cfg.intervention.layer_trace and cfg.parallel.tp > 1:
         raise ValueError("intervention.layer_trace has no tensor-parallel version (parallel.tp > 1): run it with "
                          "tp = 1")
@@ -166,6 +169,9 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
             summary["config"]["output_readout"] = True
         if runner.output_shift:
             summary["config"]["output_shift"] = True
+        if runner.output_movers:
+            summary["config"]["output_movers"] = True
+            summary["config"]["movers_k"] = runner.movers_k
         if runner.layer_trace:
             summary["config"]["layer_trace"] = True
             summary["config"]["trace_blocks"] = list(range(stack.layer, model.spec.layers))
@@ -182,7 +188,9 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
         ro_cols = ("delta_logp_out", "logp_out_spike_mean", "rank_out_min") if runner.output_readout else ()
         if runner.output_shift:
             ro_cols += ("kl_out_mean", "kl_out_spike_mean")
-        for k in ro_cols:                            # output readout / shift only: the other runs keep their columns
+        if runner.output_movers:
+            ro_cols += ("tv_out_spike_mean", "movers_up_share", "secret_loss_share")
+        for k in ro_cols:                            # the opt-in readouts only: the other runs keep their columns
             lines[0] += f",{k},{k}_lo,{k}_hi"
         for c in summary["curves"]:
             ll = c.get("ll_topk", {})
@@ -192,6 +200,24 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
                 ll.get("prompt_accuracy", ""), ll.get("any_pass", ""), ll.get("global_majority_vote", "")] +
                 [c[k][q] for k in ro_cols for q in ("mean", "lo", "hi")]))
         atomic_write_text(os.path.join(out_dir, "sweep_curves.csv"), "\n".join(lines) + "\n")
+        if runner.output_movers:                     # per (method, budget): the ten most frequent top gainers
+            from collections import Counter
+
+            import csv
+            import io
+
+            buf = io.StringIO()
+            mw = csv.writer(buf, lineterminator="\n")
+            mw.writerow(["method", "budget", "rank", "token_id", "token", "count"])
+            tops: Dict = {}
+            for r in allres:
+                if r["top_gainer"] >= 0:
+                    tops.setdefault((r["method"], r["budget"]), Counter())[r["top_gainer"]] += 1
+            for (meth, bud), cnt in sorted(tops.items()):
+                best = sorted(cnt.items(), key=lambda kv: (-kv[1], kv[0]))[:10]
+                for rank, (tid, n) in enumerate(best):
+                    mw.writerow([meth, bud, rank, tid, tok.decode([tid]), n])
+            atomic_write_text(os.path.join(out_dir, "movers_top.csv"), buf.getvalue())
         if runner.layer_trace:                       # one line per (method, budget, block)
             tl = ["method,budget,n,block,trace_dz_spike,trace_dz_spike_lo,trace_dz_spike_hi,trace_recovery,"
                   "trace_recovery_lo,trace_recovery_hi"]

@@ -158,6 +158,22 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
             if not 0.0 < cap <= 40.0:
                 raise ValueError(f"intervention.output_shift needs a final softcap in (0, 40] (the shift kernel's "
                                  f"range), not {cap}")
+        # output movers (intervention.output_movers): the tail's rows right behind a spike are also compared with their
+        # baseline rows column by column (ops.head_movers): total variation, top gainers / losers, ``movers_*`` fields
+        self.output_movers = bool(getattr(self.iv, "output_movers", False))
+        self.movers_k = int(getattr(self.iv, "movers_k", 8))
+        if self.output_movers:
+            if getattr(model, "tp", None) is not None:
+                raise ValueError("intervention.output_movers has no tensor-parallel version: run it with tp = 1")
+            if getattr(model, "head_path", False):
+                raise ValueError("intervention.output_movers has no fused-head version: run it without --fused-head")
+            cap = float(model.spec.final_softcap or 0.0)
+            if not 0.0 < cap <= 40.0:
+                raise ValueError(f"intervention.output_movers needs a final softcap in (0, 40] (the movers kernel's "
+                                 f"range), not {cap}")
+            if not 1 <= self.movers_k <= 8:
+                raise ValueError(f"intervention.movers_k must lie in 1..8 (the movers kernel's lists), not "
+                                 f"{self.movers_k}")
         # layer trace (intervention.layer_trace): the teacher-forced tail and the pairs' unedited pass also read out the
         # tracked ids' capped lens logit at every block from the hooked layer on (ops.lens_track in TraceHooks):
         # ``trace_*`` fields
@@ -184,6 +200,9 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
         self.layer_resume = cfg.runtime.layer_resume if layer_resume is None else layer_resume
         if self.output_shift and not (self.layer_resume and self.prefix_share):
             raise ValueError("intervention.output_shift is read from the layer-resumed teacher-forced tail: run it "
+                             "with layer resume and prefix sharing on (no --no-layer-resume / --no-prefix-share)")
+        if self.output_movers and not (self.layer_resume and self.prefix_share):
+            raise ValueError("intervention.output_movers is read from the layer-resumed teacher-forced tail: run it "
                              "with layer resume and prefix sharing on (no --no-layer-resume / --no-prefix-share)")
         if self.layer_trace and not (self.layer_resume and self.prefix_share):
             raise ValueError("intervention.layer_trace is read from the layer-resumed teacher-forced tail: run it "
@@ -259,6 +278,12 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
                 raise ValueError(f"intervention.layer_trace tracks at most {ops.LENS_TRACK_MAX} ids per pair (two "
                                  f"secret forms, decoys, the other words' secrets for swap runs), not {K}")
             self._n_trace = max(K, getattr(self, "_n_trace", 0))
+        if self.output_movers and pairs:
+            K = max(len(p.track) for p in pairs)
+            if K > ops.HEAD_TRACK_MAX:
+                raise ValueError(f"intervention.output_movers tracks at most {ops.HEAD_TRACK_MAX} ids per pair (two "
+                                 f"secret forms, decoys, the other words' secrets for swap runs), not {K}")
+            self._n_movers = max(K, getattr(self, "_n_movers", 0))
         return pairs
 
     def _track_cols(self) -> int:
@@ -400,6 +425,8 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
             raise ValueError("intervention.output_readout does not support the decode-tail carry-over (carry_rows > 0)")
         if self.output_shift and self.carry_rows:
             raise ValueError("intervention.output_shift does not support the decode-tail carry-over (carry_rows > 0)")
+        if self.output_movers and self.carry_rows:
+            raise ValueError("intervention.output_movers does not support the decode-tail carry-over (carry_rows > 0)")
         if self.layer_trace and self.carry_rows:
             raise ValueError("intervention.layer_trace does not support the decode-tail carry-over (carry_rows > 0)")
         if any(swap) and self.carry_rows:
@@ -517,6 +544,12 @@ def summarize_cells(results: Sequence[dict], words: Sequence[str], word_plurals:
                                      for k in range(Lt)]
             ent["trace_recovery"] = bootstrap_ci([r["trace_recovery"] for r in rs
                                                   if r["trace_recovery"] == r["trace_recovery"]], seed=bud + 10 + Lt)
+        if rs and "tv_out_spike_mean" in rs[0]:  # output movers (intervention.output_movers) only
+            for i, key in enumerate(("tv_out_spike_mean", "movers_up_share", "secret_loss_share")):
+                ent[key] = bootstrap_ci([r[key] for r in rs if r[key] == r[key]], seed=bud + 1000 + i)
+            rates = ("secret_in_losers", "decoy_in_gainers") + (("donor_in_gainers",) if meth in SWAP_METHODS else ())
+            for key in rates:
+                ent[key] = float(np.mean([r[key] for r in rs]))
         if meth in NOISE_METHODS:                # how far the control (= its targeted twin) moved the stream
             ent["edit_norm"] = float(np.mean([r["edit_norm"] for r in rs]))
         if meth in SWAP_METHODS:                 # what the transplant did to the donor's secret

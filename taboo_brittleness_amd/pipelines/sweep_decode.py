@@ -82,6 +82,9 @@ class DecodeMixin:
         if self.output_shift and batch:
             raise ValueError("intervention.output_shift needs the layer-resume path (layer resume and prefix sharing "
                              "on, the pairs' baselines resident): these cells cannot be resumed")
+        if self.output_movers and batch:
+            raise ValueError("intervention.output_movers needs the layer-resume path (layer resume and prefix sharing "
+                             "on, the pairs' baselines resident): these cells cannot be resumed")
         if self.layer_trace and batch:
             raise ValueError("intervention.layer_trace needs the layer-resume path (layer resume and prefix sharing "
                              "on, the pairs' baselines resident): these cells cannot be resumed")

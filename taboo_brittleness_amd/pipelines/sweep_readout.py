@@ -164,6 +164,9 @@ class ReadoutMixin:
         if self.output_shift:
             # the tail's per-row KLs against the baseline rows; a cell's rows start at r0 (tail row f)
             cols["shift"] = {"kl": tf.get("kl"), "kl_rev": tf.get("kl_rev"), "r0": tf["r0"][slot_a], "f": f_e}
+        if self.output_movers:
+            # the tail's compact movers outputs: a cell's selected rows (its spikes t >= f, in order) start at m0
+            cols["movers"] = {"mv": tf.get("movers"), "m0": tf["mv_m0"][slot_a], "at": tf["mv_at"], "f": f_e}
         if self.layer_trace:
             # the tail's [Lt, M, T] lens logits; a cell's rows f .. E start at r0
             cols["trace"] = {"z": tf.get("trace"), "r0": tf["r0"][slot_a], "f": f_e, "E": tf["E"][slot_a]}
@@ -250,6 +253,7 @@ class ReadoutMixin:
         ro = cols.get("ro")
         sft = cols.get("shift")
         trc = cols.get("trace")
+        mvs = cols.get("movers")
         for b, (c, p) in enumerate(zip(batch, cell_pairs)):
             ng = int(ng_a[b])
             resp = host_tok[j_a[b], :ng].tolist() if div[b] else p.resp
@@ -268,6 +272,9 @@ class ReadoutMixin:
             if sft is not None:                  # output shift only: the other runs keep their keys
                 results[-1].update(self._shift_fields(p, int(sft["f"][b]), int(sft["r0"][b]), sft["kl"],
                                                       sft["kl_rev"]))
+            if mvs is not None:                  # output movers only: the other runs keep their keys
+                results[-1].update(self._movers_fields(p, int(mvs["f"][b]), int(mvs["m0"][b]), mvs["at"], mvs["mv"],
+                                                       q if c.method in SWAP_METHODS else None))
             if trc is not None:                  # layer trace only: the other runs keep their keys
                 results[-1].update(self._trace_fields(p, int(trc["f"][b]), int(trc["E"][b]), int(trc["r0"][b]),
                                                       trc["z"], q if c.method in SWAP_METHODS else None))
@@ -443,6 +450,17 @@ class ReadoutMixin:
             res["nxt"] = host[0, :M].view(torch.int32).numpy()
             res["nll_self"] = host[1, :M].numpy()
             res["nll_tgt"] = host[2, :M].numpy()
+            mv = res.pop("_movers", None)
+            if mv is not None:               # output movers: the compact [Ms, ...] outputs ride at the very end, the
+                Ms, Km, Tm = mv              # ids as int32 bits (as the ranks do)
+                blk = flat[flat.numel() - Ms * (1 + 4 * Km + Tm):]
+                cut = np.cumsum([0, Ms, Ms * Km, Ms * Km, Ms * Km, Ms * Km, Ms * Tm])
+                part = [blk[cut[j]: cut[j + 1]] for j in range(6)]
+                res["movers"] = {"tv": part[0].numpy(), "up_id": part[1].view(torch.int32).view(Ms, Km).numpy(),
+                                 "up_dp": part[2].view(Ms, Km).numpy(),
+                                 "dn_id": part[3].view(torch.int32).view(Ms, Km).numpy(),
+                                 "dn_dp": part[4].view(Ms, Km).numpy(), "dp_track": part[5].view(Ms, Tm).numpy()}
+                flat = flat[: flat.numel() - blk.numel()]
             tr = res.pop("_trace", None)
             if tr is not None:               # layer trace: [Lt, M, T] lens logits ride behind everything else
                 res["trace"] = flat[flat.numel() - tr[0] * M * tr[1]:].view(tr[0], M, tr[1]).numpy()
@@ -506,9 +524,25 @@ class ReadoutMixin:
                "nll_tgt": np.zeros(0, np.float32), "row_cell": rb_, "row_t": t_, "tgt": tgt,
                "f": f_a, "E": E_a, "r0": r0_a, "up": up_a, "upairs": [p for p, _ in ulist], "gtab": gtab}
         trace = self.layer_trace
+        movers = self.output_movers
         first_cell = {}                      # per unique pair: a cell slot of the running batch
-        for b in range(nc - 1, -1, -1) if (trace or self.output_shift) else ():
+        for b in range(nc - 1, -1, -1) if (trace or self.output_shift or movers) else ():
             first_cell[int(up_a[b])] = b
+        mv_rows: List[int] = []              # output movers: the tail rows right behind an edited spike, cell by cell
+        mv_m0 = np.zeros(nc, np.int64)
+        if movers:
+            for b, p in enumerate(cell_pairs):
+                mv_m0[b] = len(mv_rows)
+                f, E, r0 = seg[b]
+                if E >= f:
+                    mv_rows.extend(r0 + t - f for t in p.spikes_rel if f <= t < len(p.resp))
+            res["mv_m0"] = mv_m0
+            # the compact outputs are kept in tail-row order (a head sub-chunk's selected rows are then one slice);
+            # entry j of the cell-by-cell list lives at mv_at[j]
+            mv_g = np.asarray(mv_rows, np.int64)
+            mv_ord = np.argsort(mv_g, kind="stable")
+            res["mv_at"] = np.argsort(mv_ord, kind="stable")
+            mv_g = mv_g[mv_ord]
         if M == 0:
             if trace:                        # no cell has a tail row: the records still report the baseline's trace
                 self._shift_base([p for p, _ in ulist], [first_cell[u] for u in range(len(ulist))], sync=True)
@@ -526,7 +560,12 @@ class ReadoutMixin:
         shift = self.output_shift
         Lt, Tt = (m.spec.layers - self.layer, self._n_trace) if trace else (0, 0)
         n_tr = Lt * M * Tt                   # layer trace: [Lt, M, Tt] lens logits behind the KLs
-        flat = torch.empty(3 * M + 2 * M * Kt + (2 * M if shift else 0) + n_tr, dtype=torch.float32, device=dev)
+        # output movers: tv [Ms], four [Ms, Km] lists and dp_track [Ms, Tm] behind everything else
+        Ms, Km, Tm = (len(mv_rows), self.movers_k, getattr(self, "_n_movers", 0)) if movers else (0, 0, 0)
+        n_mv = Ms * (1 + 4 * Km + Tm)
+        flat = torch.empty(3 * M + 2 * M * Kt + (2 * M if shift else 0) + n_tr + n_mv, dtype=torch.float32,
+                           device=dev)
+        end = flat.numel() - n_mv            # where the layer trace ends
         outs = flat[: 3 * M].view(3, M)
         nxt, ns, nt = outs[0].view(torch.int32), outs[1], outs[2]
         ro = None
@@ -583,37 +622,62 @@ class ReadoutMixin:
             for hk in splice:
                 hk.use_table(acts_tab, tb_d)
         sh = tr = None
-        if shift or trace:
-            # the pairs' unedited pass of blocks l+1..: the baseline side of the output shift and of the layer trace
+        if shift or trace or movers:
+            # the pairs' unedited pass of blocks l+1..: the baseline side of the output shift, of the output movers and
+            # of the layer trace
             Xb = self._shift_base([p for p, _ in ulist], [first_cell[u] for u in range(len(ulist))])
         if trace:
             # layer trace: one table block per pair of the launch, every tail row reads its pair's; the hook sits at
             # blocks l .. layers - 1 of the tail's packed pass, at block l behind the edit hook
             tr = TraceHook(self._trace_table([p for p, _ in ulist]), up_(up_a[rb_].astype(np.int32)),
-                           flat[flat.numel() - n_tr:].view(Lt, M, Tt), self.layer, m.spec.eps,
+                           flat[end - n_tr: end].view(Lt, M, Tt), self.layer, m.spec.eps,
                            float(m.spec.final_softcap or 0.0))
             hooks = {l: list(hooks.get(l, ())) + ([tr] if l in tr.layers else []) for l in set(hooks) | set(tr.layers)}
             self.stats["trace_rows"] = self.stats.get("trace_rows", 0) + Lt * M
             res["_trace"] = (Lt, Tt)
-        if shift:
-            # output shift: tail row (cell, t) is compared with its pair's unedited row t.  ``src`` already names that
-            # row in the concatenation of the pairs' rows; per head sub-chunk the distinct baseline rows and the rows'
-            # indices into them go up once, for the whole launch
-            kl_end = flat.numel() - n_tr
-            ub, rmap, uoff = [], np.zeros(M, np.int32), {}
+        if shift or movers:
+            # output shift / movers: tail row (cell, t) is compared with its pair's unedited row t.  ``src`` already
+            # names that row in the concatenation of the pairs' rows; per head sub-chunk the distinct baseline rows and
+            # the rows' indices into them go up once, for the whole launch.  Movers alone: only the sub-chunks that hold
+            # a selected row need their baseline rows
+            kl_end = end - n_tr
+            ub, rmap, uoff, moff = [], np.zeros(M, np.int32), {}, {}
             n_u = 0
+            mv_loc = np.zeros(Ms, np.int32)  # a selected row's index inside its head sub-chunk
             for (c0, c1, _chunk) in chunks:
                 for q0 in range(0, c1 - c0, step):
                     a, e = c0 + q0, min(c1, c0 + q0 + step)
+                    if movers:
+                        m0, m1 = (int(x) for x in np.searchsorted(mv_g, [a, e]))
+                        moff[a] = (m0, m1)
+                        mv_loc[m0:m1] = mv_g[m0:m1] - a
+                        if not shift and m1 == m0:
+                            continue
                     u, inv = np.unique(src[a:e], return_inverse=True)
                     ub.append(u)
                     rmap[a:e] = inv.reshape(-1)
                     uoff[a] = (n_u, n_u + u.size)
                     n_u += u.size
-            self.stats["shift_base_rows"] = self.stats.get("shift_base_rows", 0) + n_u
-            sh = {"x": Xb, "ub": up_(np.concatenate(ub).astype(np.int64)), "map": up_(rmap), "off": uoff,
-                  "kl": flat[kl_end - 2 * M: kl_end - M], "kl_rev": flat[kl_end - M: kl_end]}
-            res["_shift"] = True
+            sh = {"x": Xb, "ub": up_(np.concatenate(ub).astype(np.int64)) if ub else None, "map": up_(rmap),
+                  "off": uoff}
+            if shift:
+                self.stats["shift_base_rows"] = self.stats.get("shift_base_rows", 0) + n_u
+                sh.update({"kl": flat[kl_end - 2 * M: kl_end - M], "kl_rev": flat[kl_end - M: kl_end]})
+                res["_shift"] = True
+            if movers:
+                # the selected rows and their pairs' tracked ids (Pair.track order, -1 padded) go up once as well
+                itab = np.full((max(1, len(ulist)), max(1, Tm)), -1, np.int32)
+                for u, (p, _) in enumerate(ulist):
+                    itab[u, : len(p.track)] = p.track
+                cut = np.cumsum([end, Ms, Ms * Km, Ms * Km, Ms * Km, Ms * Km, Ms * Tm])
+                part = [flat[cut[j]: cut[j + 1]] for j in range(6)]
+                sh["mv"] = {"off": moff, "rows": up_(mv_loc), "k": Km,
+                            "ids": up_(itab[up_a[rb_[mv_g]]][:, :Tm].copy()) if Tm and Ms else None,
+                            "out": (part[0], part[1].view(torch.int32).view(Ms, Km), part[2].view(Ms, Km),
+                                    part[3].view(torch.int32).view(Ms, Km), part[4].view(Ms, Km),
+                                    part[5].view(Ms, Tm))}
+                self.stats["movers_rows"] = self.stats.get("movers_rows", 0) + Ms
+                res["_movers"] = (Ms, Km, Tm)
         try:
             self._tf_chunks(chunks, streams, tab_d, tab_off, pos_d, slot_d, tgt_d, src_d, H, ws_rows, step, hooks,
                             nxt, ns, nt, ro, sh, tr)
@@ -645,13 +709,21 @@ class ReadoutMixin:
         def shift_rows(lg, a, e):
             # the sub-chunk's distinct baseline rows through the same unembedding (whole 256-row tiles), then one pass
             # over each edited row and its baseline row
+            if a not in sh["off"]:               # movers alone, and no selected row in this sub-chunk
+                return
             u0, u1 = sh["off"][a]
             nu = u1 - u0
             xb = torch.empty(-(-nu // 256) * 256, sh["x"].shape[1], dtype=sh["x"].dtype, device=dev)
             ops.row_gather(sh["x"], sh["ub"][u0:u1], xb)
             xb[nu:].zero_()
-            ops.head_shift(lg, m.logits(xb)[:nu], sh["map"][a:e], m.spec.final_softcap, sh["kl"][a:e],
-                           sh["kl_rev"][a:e])
+            lb = m.logits(xb)[:nu]
+            if "kl" in sh:
+                ops.head_shift(lg, lb, sh["map"][a:e], m.spec.final_softcap, sh["kl"][a:e], sh["kl_rev"][a:e])
+            mv = sh.get("mv")
+            if mv is not None and mv["off"][a][1] > mv["off"][a][0]:
+                m0, m1 = mv["off"][a]
+                ops.head_movers(lg, lb, sh["map"][a:e], mv["rows"][m0:m1], m.spec.final_softcap, mv["k"],
+                                None if mv["ids"] is None else mv["ids"][m0:m1], *(o[m0:m1] for o in mv["out"]))
 
         for ci, (c0, c1, chunk) in enumerate(chunks):
             st = streams[ci % len(streams)]
@@ -711,7 +783,8 @@ class ReadoutMixin:
         from ..models.gemma2 import packed_blocks
 
         m, dev = self.m, self.dev
-        shift, trace = self.output_shift, self.layer_trace
+        # (the output movers use the output shift's baseline side: the kept final-normed rows)
+        shift, trace = self.output_shift or self.output_movers, self.layer_trace
         stale = lambda v, p: v is None or v[0] is not p.resid      # noqa: E731
         need = [(p, s) for p, s in zip(upairs, slots)
                 if ((shift and stale(p.x_base, p)) or (trace and stale(p.z_base, p))) and p.resid.shape[0]]
@@ -803,6 +876,67 @@ class ReadoutMixin:
                 "kl_out_max": max([0.0] + rows.tolist()),
                 "kl_out_spike_mean": math.fsum(hit) / len(sp) if sp else 0.0,
                 "kl_rev_out_mean": math.fsum(rrev.tolist()) / n if n else 0.0}
+
+    @staticmethod
+    def _movers_fields(p: Pair, f: int, m0: int, at: np.ndarray, mv: Optional[dict], donor: Optional[Pair]) -> dict:
+        """Record fields of the output movers for a cell whose teacher-forced tail starts at response index ``f``.
+        The cell's selected rows -- tail row ``t`` for each of its pair's spikes ``t >= f``, the rows
+        ``kl_out_spike_mean`` reads -- are entries ``m0, m0 + 1, ...`` of the launch's cell-by-cell list, entry ``j``
+        at index ``at[j]`` of the compact outputs ``mv``.  A spike before ``f`` was a no-op edit: total variation
+        exactly 0 and empty lists, not computed, and counted in the denominators as ``kl_out_spike_mean`` counts it.
+        ``movers_up`` / ``movers_dn``: per spike ``[[id, dp], ...]``; ``tv_out_spike_mean``: the mean total variation;
+        ``movers_up_share`` / ``movers_dn_share``: the mean over the spikes with ``tv > 0`` of the listed gain / loss
+        over ``tv`` (1: all the moved mass went to / came from the listed tokens; NaN without such a spike);
+        ``secret_loss_share``: over the same spikes, the larger loss of the secret's two forms over ``tv``;
+        ``secret_in_losers`` / ``decoy_in_gainers`` / ``donor_in_gainers`` (swap cells): the share of spikes whose
+        list holds a secret form / a decoy / the donor's secret; ``top_gainer``: the id with the largest summed gain
+        (the lower id on ties, -1 if none).  Sums are exactly rounded (``math.fsum``)."""
+        import math
+
+        n = len(p.resp)
+        sp = [t for t in p.spikes_rel if t < n]
+        nan = float("nan")
+        ups, dns, tvs, up_sh, dn_sh, sec_sh = [], [], [], [], [], []
+        secret = {int(t) for t in p.track[:2]}
+        decoys = {int(t) for t in p.track[2: 2 + p.n_decoys]}
+        dsec = int(donor.track[0]) if donor is not None else None
+        in_dn = in_up = in_don = 0
+        gain: Dict[int, List[float]] = {}
+        j = 0
+        for t in sp:
+            if t < f or mv is None:
+                ups.append([])
+                dns.append([])
+                tvs.append(0.0)
+                continue
+            i = int(at[m0 + j])
+            j += 1
+            up = [[int(c), float(v)] for c, v in zip(mv["up_id"][i], mv["up_dp"][i]) if c >= 0]
+            dn = [[int(c), float(v)] for c, v in zip(mv["dn_id"][i], mv["dn_dp"][i]) if c >= 0]
+            tv = float(mv["tv"][i])
+            ups.append(up)
+            dns.append(dn)
+            tvs.append(tv)
+            if tv > 0.0:
+                up_sh.append(math.fsum(v for _, v in up) / tv)
+                dn_sh.append(-math.fsum(v for _, v in dn) / tv)
+                forms = [float(x) for x in mv["dp_track"][i][:2]]
+                sec_sh.append(max(0.0, -min(forms)) / tv if forms else 0.0)
+            in_dn += any(c in secret for c, _ in dn)
+            in_up += any(c in decoys for c, _ in up)
+            in_don += dsec is not None and any(c == dsec for c, _ in up)
+            for c, v in up:
+                gain.setdefault(c, []).append(v)
+        tot = {c: math.fsum(v) for c, v in gain.items()}
+        mean = lambda xs: math.fsum(xs) / len(xs) if xs else nan       # noqa: E731
+        out = {"movers_up": ups, "movers_dn": dns,
+               "tv_out_spike_mean": math.fsum(tvs) / len(sp) if sp else 0.0,
+               "movers_up_share": mean(up_sh), "movers_dn_share": mean(dn_sh), "secret_loss_share": mean(sec_sh),
+               "secret_in_losers": in_dn / len(sp) if sp else 0.0, "decoy_in_gainers": in_up / len(sp) if sp else 0.0,
+               "top_gainer": min(tot, key=lambda c: (-tot[c], c)) if tot else -1}
+        if donor is not None:
+            out["donor_in_gainers"] = in_don / len(sp) if sp else 0.0
+        return out
 
     def _trace_table(self, upairs: Sequence[Pair]) -> torch.Tensor:
         """Layer trace: the ``[U, T, D]`` fp32 table of lens directions, one block per pair, its columns in

@@ -82,8 +82,9 @@ class Pair:
     # distribution that chose each generated token (index 0: the prefill's last prompt row), from the baseline's decode
     out_logp: Optional[np.ndarray] = None
     out_rank: Optional[np.ndarray] = None
-    # intervention.output_shift only: (the ``resid`` they were computed from, [n, D] final-normed rows of the unedited
-    # blocks past the hooked layer over ``resid``) -- the baseline side of the cells' KL (ReadoutMixin._shift_base)
+    # intervention.output_shift / output_movers only: (the ``resid`` they were computed from, [n, D] final-normed rows
+    # of the unedited blocks past the hooked layer over ``resid``) -- the baseline side of the cells' KL and of their
+    # movers (ReadoutMixin._shift_base)
     x_base: Optional[tuple] = None
     # intervention.layer_trace only: (the ``resid`` they were computed from, [n, Lt, T] fp32 host tensor: the capped lens
     # logits of ``track`` at blocks l .. layers - 1 of the same unedited pass) -- the baseline side of the cells'

@@ -13,6 +13,9 @@
 * ``fig6_layer_trace.png`` — layer trace (``intervention.layer_trace``), only for sweeps run with it: the change of the
   secret's capped lens logit at the edited rows against the block it is read at, one line per budget, targeted
   against its controls;
+* ``fig7_movers.png`` — output movers (``intervention.output_movers``), only for sweeps run with it: the share of the
+  moved probability that landed on the listed gainers and the share of it that the secret lost, vs budget / rank,
+  targeted against its controls;
 * ``table_baselines.csv`` — LL-Top-k / SAE-Top-k / token forcing rows with
   Pass@10, Majority@10, Accuracy.
 """
@@ -302,6 +305,43 @@ def layer_trace_curves(summary: Dict, path: str) -> None:
     plt.close(fig)
 
 
+def movers_curves(summary: Dict, path: str) -> None:
+    """Output movers (intervention.output_movers): ``movers_up_share`` -- the share of the total variation at the
+    edited spikes that landed on the listed top gainers (near 1: a small competition of substitutes; near 0: a diffuse
+    edit) -- and ``secret_loss_share`` -- the share of it that the secret's own forms lost -- against budget m (SAE
+    methods, top row) and rank r (subspace methods, bottom row), targeted against its controls, with 95 % bootstrap
+    intervals."""
+    curves = [c for c in summary["curves"] if "movers_up_share" in c]
+    fields = (("movers_up_share", "share of the moved mass on the listed gainers"),
+              ("secret_loss_share", "share of the moved mass lost by the secret"))
+    fig, axes = plt.subplots(2, 2, figsize=(11, 8), squeeze=False)
+    for row, (kind, xlabel) in zip(axes, (("sae", "budget m"), ("proj", "rank r"))):
+        for ax, (key, ylabel) in zip(row, fields):
+            for meth in sorted({c["method"] for c in curves if c["method"].startswith(kind + "_")}):
+                xs, ys, lo, hi = _curve(curves, meth, key)
+                if meth == "sae_splice":
+                    if ys and ys[0] == ys[0]:
+                        ax.axhline(ys[0], color="0.4", ls="--", lw=1, label="sae_splice (nothing ablated)")
+                    continue
+                ls = "o-" if meth.endswith("targeted") or meth.endswith("_swap") else "s--"
+                ax.plot(xs, ys, ls, color=_method_colour(meth), label=meth, alpha=0.9)
+                ax.fill_between(xs, lo, hi, color=_method_colour(meth), alpha=0.15)
+            ax.set_xscale("log", base=2)
+            ax.set_ylim(-0.02, 1.02)
+            ax.set_xlabel(xlabel)
+            ax.set_ylabel(ylabel)
+            ax.set_title(f"where the probability went: {kind}")
+            if ax.get_legend_handles_labels()[0]:
+                ax.legend(fontsize=7)
+    k = summary.get("config", {}).get("movers_k")
+    fig.suptitle(" | ".join(x for x in (f"top {k} gainers per spike" if k else "",
+                                        f"sae cells: {mode_label(summary)}" if mode_label(summary) else "") if x))
+    plt.tight_layout()
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    fig.savefig(path, dpi=150)
+    plt.close(fig)
+
+
 def baselines_table(rows: Dict[str, Dict[str, float]], path: str) -> None:
     lines = ["method,pass@10,majority@10,accuracy"]
     for name, m in rows.items():
@@ -346,6 +386,10 @@ def make_report(results_dir: str, out_dir: str) -> List[str]:
             if any("trace_dz_spike" in c for c in s["curves"]):    # only sweeps run with the layer trace
                 p = os.path.join(out_dir, f"fig6_layer_trace_{tag}.png")
                 layer_trace_curves(s, p)
+                made.append(p)
+            if any("movers_up_share" in c for c in s["curves"]):   # only sweeps run with the output movers
+                p = os.path.join(out_dir, f"fig7_movers_{tag}.png")
+                movers_curves(s, p)
                 made.append(p)
             if s.get("baselines"):
                 from .dashboards import write_latent_dashboard
