@@ -42,8 +42,15 @@ def main(argv=None):
                     help="also record, per edited spike, the tokens that gained and lost the most next-token "
                          "probability against the baseline and the total variation (intervention.output_movers, "
                          "intervention.movers_k; needs layer resume; no fused head, TP or decode-tail carry-over)")
+    ap.add_argument("--component-trace", action="store_true",
+                    help="also split the secret's lens logit behind each edit into the direct term and one term per "
+                         "attention head and per MLP of every later block, at the edited spike rows and the rows right "
+                         "behind them, for each cell and its baseline (intervention.component_trace; needs layer "
+                         "resume and GEMM mode tb; no TP, LoRA bank or decode-tail carry-over)")
     args = ap.parse_args(argv)
     cfg, dev = setup(args)
+    if args.component_trace:
+        cfg.intervention.component_trace = True
     if args.output_movers:
         cfg.intervention.output_movers = True
     if args.layer_trace:

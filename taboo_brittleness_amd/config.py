@@ -161,6 +161,13 @@ class InterventionCfg:
     # packed pass); adds the ``trace_*`` record fields, curves, sweep_trace.csv and fig6_layer_trace.  Needs layer
     # resume; off: records, files and launched kernels are what they are without it.
     layer_trace: bool = False
+    # component trace (opt-in): direct logit attribution behind the edit -- at each cell's edited spike rows and the rows
+    # right behind them, the secret's uncapped lens logit of the last block split into the direct term at the hooked
+    # layer and one term per attention head and per MLP of every later block, for the cell and for its baseline
+    # (ops.seg_dots in sub-hooks of the tail's packed pass); adds the ``comp_*`` record fields, summaries,
+    # sweep_components.csv and fig8_components.  Needs layer resume and, on the GPU, GEMM mode tb; off: records, files
+    # and launched kernels are what they are without it.
+    component_trace: bool = False
     # output movers (opt-in): where the probability went -- per edited spike the ``movers_k`` tokens that gained and
     # that lost the most next-token probability against the baseline's row, and the total variation between the two
     # distributions (ops.head_movers over the tail's rows right behind a spike and the baseline's rows); adds the

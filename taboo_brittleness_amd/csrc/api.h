@@ -160,6 +160,13 @@ void tb_latent_effect(const float* acts, const uint16_t* X, const float* V, int 
 // identity); latent_effect's mode-0 numerics, batch-invariant.  0 = launched; 3 = T / D out of range.
 int tb_lens_track(const uint16_t* h, const float* V, const int32_t* vrow, float* out, int M, int U, int T, int D,
                   double eps, double cap, hipStream_t st);
+// comp_trace.hip: out[i, t, s] = (sum over segment s of X[rows[i], k] W[blk[i], t, k]) / rho_i for X [M, K] bf16,
+// W [U, T, K] fp32, rows / blk [Ms] int32, S equal segments of K; rho_i = sqrt(|R[rows[i]]|^2 / Dn + eps) for
+// R [M, Dn] bf16 (null: 1), also written to rms[i].  rows[i] outside [0, M) or blk[i] outside [0, U): zeros and
+// rms[i] = 0, nothing read.  Batch-invariant.  0 = launched; 3 = T / S / K / Dn out of range.
+int tb_seg_dots(const uint16_t* X, const float* W, const int32_t* rows, const int32_t* blk, const uint16_t* R,
+                float* out, float* rms, int M, int U, int Ms, int T, int K, int S, int Dn, double eps,
+                hipStream_t st);
 // p2p.hip
 int tb_p2p_header_bytes();
 int tb_p2p_max_ranks();

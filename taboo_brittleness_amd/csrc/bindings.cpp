@@ -1111,6 +1111,39 @@ void lens_track(torch::Tensor h, torch::Tensor V, torch::Tensor vrow, torch::Ten
   TORCH_CHECK(rc == 0, "lens_track: bad arguments");
 }
 
+// component trace (comp_trace.hip): X [M, K] bf16, W [U, T, K] f32, rows / blk [Ms] int32, R [M, Dn] bf16 or none
+// -> out [Ms, T, S] f32, rms [Ms] f32
+void seg_dots(torch::Tensor X, torch::Tensor W, torch::Tensor rows, torch::Tensor blk, int64_t S,
+              c10::optional<torch::Tensor> R, torch::Tensor out, torch::Tensor rms, double eps) {
+  IN_BF16(X); IN_F32(W); IN_I32(rows); IN_I32(blk); IN_F32(out); IN_F32(rms);
+  TORCH_CHECK(X.dim() == 2 && W.dim() == 3 && W.size(2) == X.size(1), "seg_dots: X [M, K] and W [U, T, K] must share K");
+  const int64_t M = X.size(0), K = X.size(1), U = W.size(0), T = W.size(1), Ms = rows.numel();
+  TORCH_CHECK(T >= 1 && T <= 4 && S >= 1 && S <= 64, "seg_dots: 1 <= T <= 4 and 1 <= S <= 64, not ", T, " and ", S);
+  TORCH_CHECK(K >= 8 && K <= 4096 && K % 8 == 0 && K % S == 0 && (K / S) % 8 == 0,
+              "seg_dots: K and K / S must be multiples of 8 and K at most 4096, not ", K, " / ", S);
+  int64_t Dn = 0;
+  const uint16_t* rp = nullptr;
+  if (R.has_value()) {
+    const torch::Tensor& r = *R;
+    IN_BF16(r);
+    TORCH_CHECK(r.dim() == 2 && r.size(0) == M, "seg_dots: R must be [M, Dn]");
+    Dn = r.size(1);
+    TORCH_CHECK(Dn >= 8 && Dn <= 4096 && Dn % 8 == 0, "seg_dots: Dn must be a multiple of 8 and at most 4096, not ", Dn);
+    TORCH_CHECK(r.device() == X.device(), "seg_dots: one device");
+    rp = cbf(r);
+  }
+  TORCH_CHECK(M < (1LL << 31) && Ms < (1LL << 31) / 4 * 4 && U < (1LL << 31) / (T * K), "seg_dots: sizes");
+  TORCH_CHECK(blk.numel() == Ms && out.numel() == Ms * T * S && rms.numel() == Ms,
+              "seg_dots: blk must be [Ms], out [Ms, T, S] and rms [Ms]");
+  TORCH_CHECK(W.device() == X.device() && rows.device() == X.device() && blk.device() == X.device() &&
+                  out.device() == X.device() && rms.device() == X.device(), "seg_dots: one device");
+  c10::DeviceGuard g(X.device());
+  const int rc = tb_seg_dots(cbf(X), W.data_ptr<float>(), rows.data_ptr<int32_t>(), blk.data_ptr<int32_t>(), rp,
+                             out.data_ptr<float>(), rms.data_ptr<float>(), (int)M, (int)U, (int)Ms, (int)T, (int)K,
+                             (int)S, (int)Dn, eps, cur_stream());
+  TORCH_CHECK(rc == 0, "seg_dots: bad arguments");
+}
+
 int64_t attention_lds_bytes(int64_t hd) { return tb_attention_lds_bytes((int)hd); }
 
 // ---- one-shot P2P all-reduce (p2p.hip): regions are raw device pointers passed as int64
@@ -1391,6 +1424,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("latent_score", &latent_score);
   m.def("latent_effect", &latent_effect);
   m.def("lens_track", &lens_track);
+  m.def("seg_dots", &seg_dots);
   m.def("attention_lds_bytes", &attention_lds_bytes);
   m.def("p2p_alloc", &p2p_alloc);
   m.def("p2p_free", &p2p_free);

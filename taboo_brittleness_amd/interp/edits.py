@@ -63,6 +63,11 @@ the error-preserving mode only.  A plan without swap rows runs exactly the calls
 :class:`TraceHook` edits nothing: listed at the hooked layer behind the edit hook and at every later block of a packed
 pass, it reads out the capped lens logit of each row's tracked tokens (``ops.lens_track``), the layer trace of the
 sweep (``intervention.layer_trace``).
+
+:class:`ComponentHook` edits nothing either: it splits the lens logit of selected rows into the direct term at the
+hooked layer and one term per attention head and per MLP of every later block (``ops.seg_dots``), the direct logit
+attribution behind an edit.  It is listed at the hooked layer behind the edit hook, as a sub-hook
+(``forward_packed(sub_hooks=)``) at every later block, and at the last block.
 """
 from __future__ import annotations
 
@@ -470,3 +475,165 @@ class TraceHook:
         else:
             ops.lens_track(hv, self.V, self._map, self.eps, self.cap, out=self._tmp)
             self.out[k, r0:r1].copy_(self._tmp[: r1 - r0])
+
+
+def component_tables(model, first: int, ids: Sequence[Optional[int]], T: int = 2):
+    """The component trace's tables of one pair, blocks ``first + 1 .. layers - 1``: ``A [Lc, T, heads * head_dim]``
+    with ``A_b = ((1 + ln_post_attn_b) * v) @ W_o,b``, ``F [Lc, T, D]`` with ``F_b = (1 + ln_post_ffn_b) * v`` and the
+    lens directions ``Vd [T, D]`` (``v`` of ``lens_direction``), column ``j`` for ``ids[j]``; a missing or
+    out-of-vocabulary id leaves a zero column.  Built in fp64 and rounded once to fp32."""
+    from .gradient import lens_direction
+
+    w, s = model.w, model.spec
+    ids = list(ids)
+    if not 1 <= len(ids) <= T:
+        raise ValueError(f"component_tables: 1 to {T} ids, not {len(ids)}")
+    if not 0 <= first < s.layers - 1:
+        raise ValueError(f"component_tables: no block behind block {first} of {s.layers}")
+    dev = w.lm_head.device
+    v = torch.zeros(T, s.hidden, dtype=torch.float64, device=dev)
+    for j, t in enumerate(ids):
+        if t is not None and 0 <= int(t) < w.lm_head.shape[0]:
+            v[j] = lens_direction(model, [int(t)]).double()
+    A, F = [], []
+    for l in range(first + 1, s.layers):
+        L = w.layers[l]
+        A.append(((1.0 + L.ln_post_attn.double()) * v) @ L.wo.double())
+        F.append((1.0 + L.ln_post_ffn.double()) * v)
+    return torch.stack(A).float().contiguous(), torch.stack(F).float().contiguous(), v.float().contiguous()
+
+
+class ComponentHook:
+    """Component trace: per-head and per-MLP direct contributions to the lens logit of selected rows
+    (``ops.seg_dots``).  Holds the launch's tables ``A [Lc, U, T, heads * head_dim]``, ``F [Lc, U, T, D]`` and
+    ``Vd [U, T, D]`` fp32 (:func:`component_tables`, one block per pair), the selected rows ``sel [Ms]`` of the launch
+    (int32, ascending) with their table blocks ``sblk [Ms]``, and the outputs, all numerators over the sublayer's own
+    RMS but not yet over ``rho_f``:
+
+    * ``direct [Ms, T]``: ``h_l . v`` at the hooked layer ``first`` (listed there behind the edit hook);
+    * ``comp [Lc, Ms, T, heads + 1]``: heads ``0 .. heads - 1``, then the MLP, of blocks ``first + 1 .. layers - 1``
+      (:meth:`sub` listed as a sub-hook at each of them);
+    * ``total [Ms, T]`` and ``rho_f [Ms]``: ``(h_last . v) / rho_f`` and ``rho_f = rho(h_last)`` (listed at the last
+      block).
+
+    A packed forward runs one chunk of the launch's rows: :meth:`use_rows` sets the chunk's window before each
+    forward, as :meth:`TraceHook.use_rows` does.  The selection is sorted, so a window's selected rows are a slice
+    known on the host: the kernel launches over that slice alone, shapes are static per chunk and nothing syncs with
+    the host (pass ``sel_host`` with a device ``sel``)."""
+
+    def __init__(self, A: torch.Tensor, F: torch.Tensor, Vd: torch.Tensor, sel: torch.Tensor, sblk: torch.Tensor,
+                 first: int, heads: int, eps: float, out: Optional[torch.Tensor] = None,
+                 sel_host: Optional[Sequence[int]] = None):
+        if (A.dim() != 4 or F.dim() != 4 or Vd.dim() != 3 or A.shape[:3] != F.shape[:3] or A.shape[0] < 1
+                or tuple(A.shape[1:3]) != tuple(Vd.shape[:2]) or F.shape[3] != Vd.shape[2] or A.shape[3] % heads):
+            raise ValueError(f"ComponentHook: A [Lc, U, T, heads * head_dim], F [Lc, U, T, D] and Vd [U, T, D] do not "
+                             f"fit: {tuple(A.shape)}, {tuple(F.shape)}, {tuple(Vd.shape)}")
+        if sel.dtype != torch.int32 or sblk.dtype != torch.int32 or sel.dim() != 1 or sblk.shape != sel.shape:
+            raise ValueError("ComponentHook: sel and sblk must be [Ms] int32")
+        T, D = Vd.shape[1], Vd.shape[2]
+        ops.seg_dots_check(A.shape[3], heads, T, D, "ComponentHook")
+        ops.seg_dots_check(D, 1, T, D, "ComponentHook")
+        # the host's copy of the selection (``sel_host``: the caller's, so a device ``sel`` is not read back)
+        self._sel = [int(r) for r in (sel.tolist() if sel_host is None else sel_host)]
+        if len(self._sel) != sel.shape[0]:
+            raise ValueError("ComponentHook: sel_host must list the rows of sel")
+        if any(b <= a for a, b in zip(self._sel, self._sel[1:])) or (self._sel and self._sel[0] < 0):
+            raise ValueError("ComponentHook: the selected rows must be ascending launch rows")
+        self.A, self.F, self.Vd, self.sel, self.sblk = A, F, Vd, sel, sblk
+        self.first, self.heads, self.eps = int(first), int(heads), float(eps)
+        Lc, Ms, dev = A.shape[0], sel.shape[0], A.device
+        # the four outputs are views of one flat fp32 buffer (``out``: the caller's, so they can ride in its one
+        # device-to-host copy; :meth:`split` cuts the host copy the same way)
+        n = self.out_numel(Lc, Ms, T, heads)
+        if out is None:
+            out = torch.zeros(n, dtype=torch.float32, device=dev)
+        elif out.shape != (n,) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+            raise ValueError(f"ComponentHook: out must be a contiguous [{n}] float32 on the tables' device")
+        else:
+            out.zero_()
+        self.out = out
+        self.comp, self.direct, self.total, self.rho_f = self.split(out, Lc, Ms, T, heads)
+        self.calls = 0
+        self.use_rows(0, (self._sel[-1] + 1) if self._sel else 0)
+
+    @staticmethod
+    def out_numel(Lc: int, Ms: int, T: int, heads: int) -> int:
+        return Ms * (T * (Lc * (heads + 1) + 2) + 1)
+
+    @staticmethod
+    def split(flat, Lc: int, Ms: int, T: int, heads: int):
+        """``(comp [Lc, Ms, T, heads + 1], direct [Ms, T], total [Ms, T], rho_f [Ms])`` as views of a flat buffer."""
+        a = Lc * Ms * T * (heads + 1)
+        b = a + Ms * T
+        c = b + Ms * T
+        return (flat[:a].reshape(Lc, Ms, T, heads + 1), flat[a:b].reshape(Ms, T), flat[b:c].reshape(Ms, T),
+                flat[c:c + Ms])
+
+    @property
+    def layers(self) -> range:
+        """The blocks whose sublayers are read."""
+        return range(self.first + 1, self.first + 1 + self.A.shape[0])
+
+    @property
+    def last(self) -> int:
+        return self.first + self.A.shape[0]
+
+    def use_rows(self, r0: int, r1: int, padded: Optional[int] = None) -> None:
+        """The next forwards run rows ``[r0, r1)`` of the launch, followed by padding rows up to ``padded`` rows."""
+        import bisect
+
+        n = r1 - r0
+        padded = n if padded is None else int(padded)
+        if not 0 <= r0 <= r1 or padded < n:
+            raise ValueError(f"ComponentHook.use_rows: window [{r0}, {r1}) padded to {padded}")
+        i0, i1 = bisect.bisect_left(self._sel, r0), bisect.bisect_left(self._sel, r1)
+        self._sl, self._n = (i0, i1), padded
+        k, T, dev = i1 - i0, self.Vd.shape[1], self.sel.device
+        self._rows = self.sel[i0:i1] - r0
+        self._blk = self.sblk[i0:i1].contiguous()
+        self._th = torch.empty(k, T, self.heads, dtype=torch.float32, device=dev)
+        self._t1 = torch.empty(k, T, 1, dtype=torch.float32, device=dev)
+        self._rms = torch.empty(k, dtype=torch.float32, device=dev)
+
+    def _rows_of(self, t: torch.Tensor, what: str) -> torch.Tensor:
+        v = t.view(-1, t.shape[-1])
+        if v.shape[0] != self._n:
+            raise ValueError(f"ComponentHook: the forward has {v.shape[0]} {what} rows, the window set by use_rows "
+                             f"{self._n}")
+        return v
+
+    def __call__(self, h: torch.Tensor, x: torch.Tensor, ctx) -> None:
+        if ctx.layer not in (self.first, self.last):
+            raise ValueError(f"ComponentHook: called at block {ctx.layer}, listed at blocks {self.first} and "
+                             f"{self.last}")
+        hv = self._rows_of(h, "residual")
+        i0, i1 = self._sl
+        if i0 == i1:
+            return
+        self.calls += 1
+        if ctx.layer == self.first:
+            ops.seg_dots(hv, self.Vd, self._rows, self._blk, 1, None, self.eps, out=self._t1, rms=self._rms)
+            self.direct[i0:i1].copy_(self._t1[:, :, 0])
+        else:
+            ops.seg_dots(hv, self.Vd, self._rows, self._blk, 1, hv, self.eps, out=self._t1, rms=self._rms)
+            self.total[i0:i1].copy_(self._t1[:, :, 0])
+            self.rho_f[i0:i1].copy_(self._rms)
+
+    def sub(self, kind: str, inp: torch.Tensor, o: torch.Tensor, ctx) -> None:
+        """The sub-hook: ``("attn", ws.attn, ws.o)`` and ``("ffn", ws.act, ws.o)`` of a block in :attr:`layers`."""
+        k = ctx.layer - self.first - 1
+        if not 0 <= k < self.A.shape[0] or kind not in ("attn", "ffn"):
+            raise ValueError(f"ComponentHook.sub: {kind!r} at block {ctx.layer}, reads attn / ffn of blocks "
+                             f"{self.first + 1}..{self.last}")
+        ov = self._rows_of(o, "sublayer")
+        i0, i1 = self._sl
+        if i0 == i1:
+            return
+        self.calls += 1
+        if kind == "attn":
+            ops.seg_dots(self._rows_of(inp, "attention"), self.A[k], self._rows, self._blk, self.heads, ov, self.eps,
+                         out=self._th, rms=self._rms)
+            self.comp[k, i0:i1, :, : self.heads].copy_(self._th)
+        else:
+            ops.seg_dots(ov, self.F[k], self._rows, self._blk, 1, ov, self.eps, out=self._t1, rms=self._rms)
+            self.comp[k, i0:i1, :, self.heads].copy_(self._t1[:, :, 0])

@@ -33,10 +33,12 @@ import torch
 
 from .. import ops
 from ..ops import reference as ref
+from ..runtime import gemm_dispatch as _GD
 from .spec import Gemma2Spec
 from .weights import Gemma2Weights
 
 Hook = Callable[[torch.Tensor, torch.Tensor, "HookCtx"], None]
+SubHook = Callable[[str, torch.Tensor, torch.Tensor, "HookCtx"], None]     # (kind, sublayer input, raw output, ctx)
 
 
 @dataclass
@@ -312,7 +314,8 @@ class Gemma2Model:
                        blk: torch.Tensor, cache: KVCache, hooks: Optional[Dict[int, Sequence[Hook]]] = None,
                        stop_at: Optional[int] = None, ws: Optional[_Workspace] = None,
                        resume_after: Optional[int] = None, h_in: Optional[torch.Tensor] = None,
-                       prefix_kv: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:
+                       prefix_kv: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                       sub_hooks: Optional[Dict[int, Sequence[SubHook]]] = None) -> torch.Tensor:
         """Ragged forward over packed rows ``ids [M]`` (no padding between sequences): row ``i`` sits at
         position ``pos[i]`` of cache slot ``slot_rows[i]``; ``blk`` is the attention block table
         (:func:`packed_blocks`).  Hooks see every row as its own length-1 sequence (``ctx.B = M``,
@@ -324,7 +327,13 @@ class Gemma2Model:
         (the exact layer-resume of prefix-shared sweep cells).
 
         ``prefix_kv = (k, v)`` (``[L, P, Hkv, S, HD]``) with a 5-column ``blk``: each block reads its keys
-        below its prefix length from its prefix slot of ``k/v`` (no copy into the row's own slot)."""
+        below its prefix length from its prefix slot of ``k/v`` (no copy into the row's own slot).
+
+        ``sub_hooks[l]`` are called inside block ``l``, where the sublayers' rows are still live:
+        ``hk("attn", ws.attn, ws.o, ctx)`` right after ``o_proj`` + norm (the heads' outputs before ``o_proj`` and
+        the raw projection output) and ``hk("ffn", ws.act, ws.o, ctx)`` right after ``down`` + norm.  They read
+        only.  ``ws.o`` holds the projection unless the GEMM dispatch folds split-K partials into the norm, which
+        the exact ``tb`` mode never does: on the GPU any other mode raises."""
         M = pos.numel()
         ws = ws or self.workspace(M)
         ws.slot_rows.copy_(slot_rows.view(M))
@@ -337,12 +346,17 @@ class Gemma2Model:
 
         if resume_after is not None:
             return self._run(None, pos.reshape(M), cache, ws, attn, hooks, stop_at, M, 1, sr,
-                             start=resume_after, h_in=h_in)
-        return self._run(ids.reshape(M), pos.reshape(M), cache, ws, attn, hooks, stop_at, M, 1, sr)
+                             start=resume_after, h_in=h_in, sub_hooks=sub_hooks)
+        return self._run(ids.reshape(M), pos.reshape(M), cache, ws, attn, hooks, stop_at, M, 1, sr,
+                         sub_hooks=sub_hooks)
 
     def _run(self, ids32, pos32, cache, ws, attn, hooks, stop_at, B, T, ctx_slot, start: Optional[int] = None,
-             h_in: Optional[torch.Tensor] = None, slot_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+             h_in: Optional[torch.Tensor] = None, slot_rows: Optional[torch.Tensor] = None,
+             sub_hooks: Optional[Dict[int, Sequence[SubHook]]] = None) -> torch.Tensor:
         s = self.spec
+        if sub_hooks and ws.h.is_cuda and _GD.mode() != "tb":
+            raise ValueError(f"sub_hooks read ws.o, which holds the projection output in GEMM mode tb only, not "
+                             f"{_GD.mode()!r}")
         slot_rows = ws.slot_rows if slot_rows is None else slot_rows
         ls = self.lspec
         w = self.w
@@ -404,6 +418,10 @@ class Gemma2Model:
                 if self.tp is not None:
                     self.tp.all_reduce_(ws.o)
                 ops.add_rmsnorm2(h, ws.o, L.ln_post_attn, L.ln_pre_ffn, s.eps, out=x)
+            if sub_hooks and l in sub_hooks:
+                sctx = HookCtx(l, B, T, pos32, ctx_slot, L.ln_pre_ffn, s.eps, self)
+                for hk in sub_hooks[l]:
+                    hk("attn", ws.attn, ws.o, sctx)
             if "gu" in F:
                 A_, W_, n_ = F["gu"]
                 ops.lora_t(x, A_, arow, n_, nr, rr, out=lt["gu"])
@@ -433,6 +451,10 @@ class Gemma2Model:
                 if self.tp is not None:
                     self.tp.all_reduce_(ws.o)
                 ops.add_rmsnorm2(h, ws.o, L.ln_post_ffn, self.norm_next[l], s.eps, out=x)
+            if sub_hooks and l in sub_hooks:
+                sctx = HookCtx(l, B, T, pos32, ctx_slot, self.norm_next[l], s.eps, self)
+                for hk in sub_hooks[l]:
+                    hk("ffn", ws.act, ws.o, sctx)
             if hooks and l in hooks:
                 ctx = HookCtx(l, B, T, pos32, ctx_slot, self.norm_next[l], s.eps, self)
                 for hk in hooks[l]:

@@ -996,3 +996,65 @@ def lens_track(h, V, vrow, eps, cap, out=None):
         return out
     out.copy_(ref.lens_track(h, V, vrow, eps, cap))
     return out
+
+
+SEG_DOTS_MAX_T, SEG_DOTS_MAX_S, SEG_DOTS_MAX_K = 4, 64, 4096     # csrc/comp_trace.hip
+
+
+def seg_dots_check(K, S, T, Dn=None, what="seg_dots"):
+    """Raise ``ValueError`` unless ``(K, S, T, Dn)`` is inside the kernel's range (csrc/comp_trace.hip)."""
+    if not 1 <= T <= SEG_DOTS_MAX_T:
+        raise ValueError(f"{what}: 1 <= T <= {SEG_DOTS_MAX_T} table columns, not {T}")
+    if not 1 <= S <= SEG_DOTS_MAX_S:
+        raise ValueError(f"{what}: 1 <= S <= {SEG_DOTS_MAX_S} segments, not {S}")
+    if K % 8 != 0 or not 8 <= K <= SEG_DOTS_MAX_K or K % S != 0 or (K // S) % 8 != 0:
+        raise ValueError(f"{what}: K and K / S must be multiples of 8 and K at most {SEG_DOTS_MAX_K}, not K = {K}, "
+                         f"S = {S}")
+    if Dn is not None and (Dn % 8 != 0 or not 8 <= Dn <= SEG_DOTS_MAX_K):
+        raise ValueError(f"{what}: Dn must be a multiple of 8 and at most {SEG_DOTS_MAX_K}, not {Dn}")
+
+
+def seg_dots(X, W, rows, blk, S, R, eps, out=None, rms=None):
+    """Segment-wise dot products of selected rows over the rows' RMS (csrc/comp_trace.hip): ``out[i, t, s] =
+    (sum_{k in segment s} X[rows[i], k] W[blk[i], t, k]) / rho_i`` with ``rho_i = sqrt(|R[rows[i]]|^2 / Dn + eps)``
+    (``R = None``: 1) and ``rms[i] = rho_i``, for ``X [M, K]`` bf16, a table ``W [U, T, K]`` fp32, ``rows [Ms]`` and
+    ``blk [Ms]`` int32, ``R [M, Dn]`` bf16; segment ``s`` is columns ``[s K / S, (s + 1) K / S)``.  A selected row
+    with ``rows[i]`` outside ``[0, M)`` or ``blk[i]`` outside ``[0, U)`` gets +0.0 in every column and ``rms[i] =
+    0.0`` and reads nothing; an all-zero table segment gives exactly +0.0.  A row's bits depend on that row, its table
+    block and ``(K, S, T, Dn)`` alone.  ``1 <= T <= 4``, ``1 <= S <= 64``, ``K % 8 == 0``, ``(K / S) % 8 == 0``,
+    ``K, Dn <= 4096``, ``Dn % 8 == 0``; anything else raises ``ValueError``.  Returns ``(out [Ms, T, S], rms [Ms])``
+    fp32."""
+    if X.dim() != 2 or W.dim() != 3 or W.shape[2] != X.shape[1]:
+        raise ValueError(f"seg_dots: X [M, K] and W [U, T, K] must share K, got {tuple(X.shape)} and {tuple(W.shape)}")
+    M, K = X.shape
+    T = W.shape[1]
+    S = int(S)
+    if R is not None and (R.dim() != 2 or R.shape[0] != M):
+        raise ValueError(f"seg_dots: R must be [M={M}, Dn], got {tuple(R.shape)}")
+    seg_dots_check(K, S, T, None if R is None else R.shape[1])
+    if X.dtype != BF16 or W.dtype != torch.float32 or (R is not None and R.dtype != BF16):
+        raise ValueError(f"seg_dots: X and R must be bf16 and W float32, got {X.dtype}, "
+                         f"{None if R is None else R.dtype} and {W.dtype}")
+    if rows.dtype != torch.int32 or blk.dtype != torch.int32 or rows.dim() != 1 or blk.shape != rows.shape:
+        raise ValueError(f"seg_dots: rows and blk must be [Ms] int32, got {tuple(rows.shape)} {rows.dtype} and "
+                         f"{tuple(blk.shape)} {blk.dtype}")
+    Ms = rows.shape[0]
+    dev = X.device
+    if any(t is not None and t.device != dev for t in (W, rows, blk, R)):
+        raise ValueError("seg_dots: X, W, rows, blk and R must be on one device")
+    for t, shape, name in ((out, (Ms, T, S), "out"), (rms, (Ms,), "rms")):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != dev
+                              or not t.is_contiguous()):
+            raise ValueError(f"seg_dots: {name} must be a contiguous {list(shape)} float32 on X's device")
+    out = _out(out, (Ms, T, S), torch.float32, dev)
+    rms = _out(rms, (Ms,), torch.float32, dev)
+    if Ms == 0:
+        return out, rms
+    if X.is_cuda:
+        _k().seg_dots(X.contiguous(), W.contiguous(), rows.contiguous(), blk.contiguous(), S,
+                      None if R is None else R.contiguous(), out, rms, float(eps))
+        return out, rms
+    o, r = ref.seg_dots(X, W, rows, blk, S, R, eps)
+    out.copy_(o)
+    rms.copy_(r)
+    return out, rms

@@ -673,6 +673,33 @@ def lens_track(h: torch.Tensor, V: torch.Tensor, vrow: torch.Tensor, eps: float,
     return out
 
 
+def seg_dots(X: torch.Tensor, W: torch.Tensor, rows: torch.Tensor, blk: torch.Tensor, S: int,
+             R: Optional[torch.Tensor], eps: float):
+    """Reference of ``ops.seg_dots`` in fp64, as the explicit formula: ``out[i, t, s] = (sum_{k in segment s}
+    X[rows[i], k] W[blk[i], t, k]) / rho_i``, ``rho_i = sqrt(|R[rows[i]]|^2 / Dn + eps)`` (1 without ``R``).  Selected
+    rows with ``rows[i]`` outside ``[0, M)`` or ``blk[i]`` outside ``[0, U)`` are 0, their ``rho`` too.
+    ``(out [Ms, T, S], rms [Ms])`` fp64."""
+    M, K = X.shape
+    U, T = W.shape[0], W.shape[1]
+    Ms, S = rows.shape[0], int(S)
+    r, u = rows.long(), blk.long()
+    ok = (r >= 0) & (r < M) & (u >= 0) & (u < U)
+    out = torch.zeros(Ms, T, S, dtype=torch.float64, device=X.device)
+    rms = torch.zeros(Ms, dtype=torch.float64, device=X.device)
+    sel = torch.nonzero(ok).flatten()
+    Wd = W.double()
+    for i0 in range(0, sel.numel(), 256):       # elementwise products summed per (row, t, s): no row sees another
+        i = sel[i0:i0 + 256]
+        x = X[r[i]].double()
+        rho = torch.ones(i.numel(), dtype=torch.float64, device=X.device)
+        if R is not None:
+            rho = torch.sqrt(R[r[i]].double().pow(2).sum(-1) / R.shape[1] + float(eps))
+        prod = (x[:, None, :] * Wd[u[i]]).view(i.numel(), T, S, K // S)
+        out[i] = prod.sum(-1) / rho[:, None, None]
+        rms[i] = rho
+    return out, rms
+
+
 def vp_head_merge(st: torch.Tensor, tgt, V: int):
     """Reference of ``ops.vp_head_merge`` (rank order; on equal best logits the lower rank = lower vocab id)."""
     tp, R = st.shape[0], st.shape[1]

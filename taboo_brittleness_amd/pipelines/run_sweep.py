@@ -54,6 +54,9 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
     if cfg.intervention.output_movers and cfg.parallel.tp > 1:
         raise ValueError("intervention.output_movers has no tensor-parallel version (parallel.tp > 1): run it with "
                          "tp = 1")
+    if cfg.intervention.component_trace and cfg.parallel.tp > 1:
+        raise ValueError("intervention.component_trace has no tensor-parallel version (parallel.tp > 1): run it with "
+                         "tp = 1")
     if cfg.intervention.layer_trace and cfg.parallel.tp > 1:
         raise ValueError("intervention.layer_trace has no tensor-parallel version (parallel.tp > 1): run it with "
                          "tp = 1")
@@ -175,6 +178,10 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
         if runner.layer_trace:
             summary["config"]["layer_trace"] = True
             summary["config"]["trace_blocks"] = list(range(stack.layer, model.spec.layers))
+        if runner.component_trace:
+            summary["config"]["component_trace"] = True
+            summary["config"]["comp_blocks"] = list(range(stack.layer + 1, model.spec.layers))
+            summary["config"]["comp_names"] = [f"h{j}" for j in range(model.lspec.heads)] + ["mlp"]
         if swap:
             summary["config"]["swap_donor"] = runner.swap_donor
             summary["swap_skipped"] = [{"word": w, "prompt_idx": i} for w, i in runner.swap_skipped]
@@ -218,6 +225,13 @@ def run_sweep(cfg: Config, out_dir: str, methods: Sequence[str] = METHODS, info:
                 for rank, (tid, n) in enumerate(best):
                     mw.writerow([meth, bud, rank, tid, tok.decode([tid]), n])
             atomic_write_text(os.path.join(out_dir, "movers_top.csv"), buf.getvalue())
+        if runner.component_trace:                   # one line per (method, budget, block, component)
+            cl = ["method,budget,n,block,component,mean"]
+            for c in summary["curves"]:
+                for blk, row in zip(summary["config"]["comp_blocks"], c["comp_dz_spike"]):
+                    for name, v in zip(summary["config"]["comp_names"], row):
+                        cl.append(",".join(str(x) for x in [c["method"], c["budget"], c["n"], blk, name, v]))
+            atomic_write_text(os.path.join(out_dir, "sweep_components.csv"), "\n".join(cl) + "\n")
         if runner.layer_trace:                       # one line per (method, budget, block)
             tl = ["method,budget,n,block,trace_dz_spike,trace_dz_spike_lo,trace_dz_spike_hi,trace_recovery,"
                   "trace_recovery_lo,trace_recovery_hi"]

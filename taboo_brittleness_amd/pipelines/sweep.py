@@ -69,6 +69,12 @@ coincide with the target's row where their spikes coincide: that spike is an exa
 lens logit, or its first-order attribution to the model's own logit); cells, seeds, random pools and every reuse
 level are those of the default ``corr``.
 
+``intervention.component_trace`` (opt-in) says which component behind the edit moved the secret: at every cell's edited
+spike rows and the rows right behind them, the same two passes carry a :class:`~..interp.edits.ComponentHook` that
+splits the uncapped lens logit of the last block's residual into the direct term at block ``l`` and one term per
+attention head and per MLP of blocks ``l+1 ..`` (``ops.seg_dots``); the records' ``comp_*`` fields are the differences
+edited minus baseline, each run over its own final RMS.
+
 ``intervention.layer_trace`` (opt-in) reads the blocks between the edit and the output: the teacher-forced tail and the
 pairs' unedited pass of blocks ``l+1..`` carry a :class:`~..interp.edits.TraceHook` at blocks ``l .. layers - 1`` that
 writes the capped lens logit of every row's tracked ids (``ops.lens_track``); the records' ``trace_*`` fields are the
@@ -184,6 +190,31 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
             if model.spec.hidden % 8 or model.spec.hidden > 4096:
                 raise ValueError(f"intervention.layer_trace needs a residual width that is a multiple of 8 and at most "
                                  f"4096 (the trace kernel's range), not {model.spec.hidden}")
+        # component trace (intervention.component_trace): at the cells' edited spike rows and the rows behind them, the
+        # tail and the pairs' unedited pass also split the secret's lens logit into the direct term and one term per
+        # head and per MLP of every later block (ops.seg_dots in a ComponentHook): ``comp_*`` fields
+        self.component_trace = bool(getattr(self.iv, "component_trace", False))
+        if self.component_trace:
+            from ..runtime import gemm_dispatch as _GD
+
+            if getattr(model, "tp", None) is not None:
+                raise ValueError("intervention.component_trace has no tensor-parallel version: run it with tp = 1")
+            if getattr(model, "lora", None) is not None:
+                raise ValueError("intervention.component_trace does not support the LoRA bank: a head's path through "
+                                 "W_o + B A is not in its table")
+            if not 0 <= self.layer < model.spec.layers - 1:
+                raise ValueError(f"intervention.component_trace reads the blocks behind the hooked layer: block "
+                                 f"{self.layer} is the last of {model.spec.layers}")
+            ls = model.lspec
+            try:
+                what = "intervention.component_trace"
+                ops.seg_dots_check(ls.heads * ls.head_dim, ls.heads, 2, model.spec.hidden, what)
+                ops.seg_dots_check(model.spec.hidden, 1, 2, model.spec.hidden, what)
+            except ValueError as e:
+                raise ValueError(f"{e} (the component kernel's range)") from None
+            if self.dev.type == "cuda" and _GD.mode() != "tb":
+                raise ValueError(f"intervention.component_trace reads the raw o_proj / down outputs, which the "
+                                 f"workspace holds in GEMM mode tb only, not {_GD.mode()!r}")
         self.exclusion = exclusion
         self.use_graphs = use_graphs
         self.prefix_share = cfg.runtime.prefix_share if prefix_share is None else prefix_share
@@ -203,6 +234,9 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
                              "with layer resume and prefix sharing on (no --no-layer-resume / --no-prefix-share)")
         if self.output_movers and not (self.layer_resume and self.prefix_share):
             raise ValueError("intervention.output_movers is read from the layer-resumed teacher-forced tail: run it "
+                             "with layer resume and prefix sharing on (no --no-layer-resume / --no-prefix-share)")
+        if self.component_trace and not (self.layer_resume and self.prefix_share):
+            raise ValueError("intervention.component_trace is read from the layer-resumed teacher-forced tail: run it "
                              "with layer resume and prefix sharing on (no --no-layer-resume / --no-prefix-share)")
         if self.layer_trace and not (self.layer_resume and self.prefix_share):
             raise ValueError("intervention.layer_trace is read from the layer-resumed teacher-forced tail: run it "
@@ -427,6 +461,9 @@ class SweepRunner(PlanMixin, DecodeMixin, ReadoutMixin):
             raise ValueError("intervention.output_shift does not support the decode-tail carry-over (carry_rows > 0)")
         if self.output_movers and self.carry_rows:
             raise ValueError("intervention.output_movers does not support the decode-tail carry-over (carry_rows > 0)")
+        if self.component_trace and self.carry_rows:
+            raise ValueError("intervention.component_trace does not support the decode-tail carry-over "
+                             "(carry_rows > 0)")
         if self.layer_trace and self.carry_rows:
             raise ValueError("intervention.layer_trace does not support the decode-tail carry-over (carry_rows > 0)")
         if any(swap) and self.carry_rows:
@@ -544,6 +581,11 @@ def summarize_cells(results: Sequence[dict], words: Sequence[str], word_plurals:
                                      for k in range(Lt)]
             ent["trace_recovery"] = bootstrap_ci([r["trace_recovery"] for r in rs
                                                   if r["trace_recovery"] == r["trace_recovery"]], seed=bud + 10 + Lt)
+        if rs and "comp_dz_spike" in rs[0]:      # component trace (intervention.component_trace) only
+            Lc = len(rs[0]["comp_dz_spike"])
+            ent["comp_dz_spike"] = np.mean([r["comp_dz_spike"] for r in rs], axis=0).tolist()   # [Lc][heads + 1]
+            for i, key in enumerate(("comp_attn_dz_spike", "comp_mlp_dz_spike")):
+                ent[key] = [bootstrap_ci([r[key][k] for r in rs], seed=bud + 2000 + i * Lc + k) for k in range(Lc)]
         if rs and "tv_out_spike_mean" in rs[0]:  # output movers (intervention.output_movers) only
             for i, key in enumerate(("tv_out_spike_mean", "movers_up_share", "secret_loss_share")):
                 ent[key] = bootstrap_ci([r[key] for r in rs if r[key] == r[key]], seed=bud + 1000 + i)

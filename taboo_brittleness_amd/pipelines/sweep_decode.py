@@ -85,6 +85,9 @@ class DecodeMixin:
         if self.output_movers and batch:
             raise ValueError("intervention.output_movers needs the layer-resume path (layer resume and prefix sharing "
                              "on, the pairs' baselines resident): these cells cannot be resumed")
+        if self.component_trace and batch:
+            raise ValueError("intervention.component_trace needs the layer-resume path (layer resume and prefix "
+                             "sharing on, the pairs' baselines resident): these cells cannot be resumed")
         if self.layer_trace and batch:
             raise ValueError("intervention.layer_trace needs the layer-resume path (layer resume and prefix sharing "
                              "on, the pairs' baselines resident): these cells cannot be resumed")

@@ -340,6 +340,8 @@ class PlanMixin:
                 raise ValueError("swap methods need pairs that track the other words' secrets: "
                                  "build_pairs(words, prompts, methods)")
             donors = self.swap_donors(pairs)
+            if getattr(self, "component_trace", False):     # the donor column of the pairs' component tables
+                self._pair_donor = {id(p): pairs[d].word for p, d in zip(pairs, donors) if d >= 0}
             self.swap_skipped = [(p.word, p.pidx) for p, d in zip(pairs, donors) if d < 0]
         for pi, p in enumerate(pairs):
             for meth in methods:

@@ -12,7 +12,7 @@ import torch
 
 from .. import ops
 from ..interp import analysis as A
-from ..interp.edits import EditHook, TraceHook
+from ..interp.edits import ComponentHook, EditHook, TraceHook, component_tables
 from ..interp.logit_lens import excl_table, lens_packed, lens_readout, reference_exclusions, vocab_slice, vocab_topk
 from ..interp.prompts import contains_secret
 from .sweep_types import NOISE_METHODS, SWAP_METHODS, Cell, Pair, _h2d, _nullctx
@@ -167,6 +167,9 @@ class ReadoutMixin:
         if self.output_movers:
             # the tail's compact movers outputs: a cell's selected rows (its spikes t >= f, in order) start at m0
             cols["movers"] = {"mv": tf.get("movers"), "m0": tf["mv_m0"][slot_a], "at": tf["mv_at"], "f": f_e}
+        if self.component_trace:
+            # the tail's component slabs over its selected rows: a cell's rows (response indices ts) start at i0
+            cols["comp"] = {"c": tf.get("comp"), "i0": tf["ct_i0"][slot_a], "ts": [tf["ct_ts"][s] for s in slot_a]}
         if self.layer_trace:
             # the tail's [Lt, M, T] lens logits; a cell's rows f .. E start at r0
             cols["trace"] = {"z": tf.get("trace"), "r0": tf["r0"][slot_a], "f": f_e, "E": tf["E"][slot_a]}
@@ -254,6 +257,7 @@ class ReadoutMixin:
         sft = cols.get("shift")
         trc = cols.get("trace")
         mvs = cols.get("movers")
+        cmp_ = cols.get("comp")
         for b, (c, p) in enumerate(zip(batch, cell_pairs)):
             ng = int(ng_a[b])
             resp = host_tok[j_a[b], :ng].tolist() if div[b] else p.resp
@@ -275,6 +279,9 @@ class ReadoutMixin:
             if mvs is not None:                  # output movers only: the other runs keep their keys
                 results[-1].update(self._movers_fields(p, int(mvs["f"][b]), int(mvs["m0"][b]), mvs["at"], mvs["mv"],
                                                        q if c.method in SWAP_METHODS else None))
+            if cmp_ is not None:                 # component trace only: the other runs keep their keys
+                results[-1].update(self._comp_fields(p, int(cmp_["i0"][b]), cmp_["ts"][b], cmp_["c"],
+                                                     c.method in SWAP_METHODS))
             if trc is not None:                  # layer trace only: the other runs keep their keys
                 results[-1].update(self._trace_fields(p, int(trc["f"][b]), int(trc["E"][b]), int(trc["r0"][b]),
                                                       trc["z"], q if c.method in SWAP_METHODS else None))
@@ -450,8 +457,13 @@ class ReadoutMixin:
             res["nxt"] = host[0, :M].view(torch.int32).numpy()
             res["nll_self"] = host[1, :M].numpy()
             res["nll_tgt"] = host[2, :M].numpy()
+            ct = res.pop("_comp", None)
+            if ct is not None:               # component trace: the hook's flat output buffer rides at the very end
+                n_ct = ComponentHook.out_numel(*ct)
+                res["comp"] = tuple(t.numpy() for t in ComponentHook.split(flat[flat.numel() - n_ct:], *ct))
+                flat = flat[: flat.numel() - n_ct]
             mv = res.pop("_movers", None)
-            if mv is not None:               # output movers: the compact [Ms, ...] outputs ride at the very end, the
+            if mv is not None:               # output movers: the compact [Ms, ...] outputs ride behind the trace, the
                 Ms, Km, Tm = mv              # ids as int32 bits (as the ranks do)
                 blk = flat[flat.numel() - Ms * (1 + 4 * Km + Tm):]
                 cut = np.cumsum([0, Ms, Ms * Km, Ms * Km, Ms * Km, Ms * Km, Ms * Tm])
@@ -543,8 +555,23 @@ class ReadoutMixin:
             mv_ord = np.argsort(mv_g, kind="stable")
             res["mv_at"] = np.argsort(mv_ord, kind="stable")
             mv_g = mv_g[mv_ord]
+        comp = self.component_trace
+        if comp and not first_cell:
+            for b in range(nc - 1, -1, -1):
+                first_cell[int(up_a[b])] = b
+        ct_rows: List[int] = []              # component trace: the tail rows at and right behind an edited spike
+        if comp:
+            ct_i0, ct_ts = np.zeros(nc, np.int64), []
+            for b, p in enumerate(cell_pairs):
+                ct_i0[b] = len(ct_rows)
+                f, E, r0 = seg[b]
+                hi = min(E, len(p.resp) - 1)
+                ts = sorted({u for t in p.spikes_rel if f <= t <= hi for u in (t, t + 1) if u <= hi})
+                ct_ts.append(np.asarray(ts, np.int64))
+                ct_rows.extend(r0 + t - f for t in ts)
+            res["ct_i0"], res["ct_ts"] = ct_i0, ct_ts
         if M == 0:
-            if trace:                        # no cell has a tail row: the records still report the baseline's trace
+            if trace or comp:                # no cell has a tail row: the records still report the baseline's side
                 self._shift_base([p for p, _ in ulist], [first_cell[u] for u in range(len(ulist))], sync=True)
             return res
         dev = self.dev
@@ -563,9 +590,12 @@ class ReadoutMixin:
         # output movers: tv [Ms], four [Ms, Km] lists and dp_track [Ms, Tm] behind everything else
         Ms, Km, Tm = (len(mv_rows), self.movers_k, getattr(self, "_n_movers", 0)) if movers else (0, 0, 0)
         n_mv = Ms * (1 + 4 * Km + Tm)
-        flat = torch.empty(3 * M + 2 * M * Kt + (2 * M if shift else 0) + n_tr + n_mv, dtype=torch.float32,
+        # component trace: the hook's slabs over the selected rows at the very end
+        ct_dims = (m.spec.layers - 1 - self.layer, len(ct_rows), 2, m.lspec.heads) if comp else None
+        n_ct = ComponentHook.out_numel(*ct_dims) if comp else 0
+        flat = torch.empty(3 * M + 2 * M * Kt + (2 * M if shift else 0) + n_tr + n_mv + n_ct, dtype=torch.float32,
                            device=dev)
-        end = flat.numel() - n_mv            # where the layer trace ends
+        end = flat.numel() - n_mv - n_ct     # where the layer trace ends
         outs = flat[: 3 * M].view(3, M)
         nxt, ns, nt = outs[0].view(torch.int32), outs[1], outs[2]
         ro = None
@@ -621,8 +651,8 @@ class ReadoutMixin:
             tb_d = up_(tb)
             for hk in splice:
                 hk.use_table(acts_tab, tb_d)
-        sh = tr = None
-        if shift or trace or movers:
+        sh = tr = ct = None
+        if shift or trace or movers or comp:
             # the pairs' unedited pass of blocks l+1..: the baseline side of the output shift, of the output movers and
             # of the layer trace
             Xb = self._shift_base([p for p, _ in ulist], [first_cell[u] for u in range(len(ulist))])
@@ -635,6 +665,17 @@ class ReadoutMixin:
             hooks = {l: list(hooks.get(l, ())) + ([tr] if l in tr.layers else []) for l in set(hooks) | set(tr.layers)}
             self.stats["trace_rows"] = self.stats.get("trace_rows", 0) + Lt * M
             res["_trace"] = (Lt, Tt)
+        if comp:
+            # component trace: one table block per pair of the launch; the hook sits at block l behind the edit hook,
+            # inside every later block and at the last block, and reads the selected rows alone
+            sel = np.asarray(ct_rows, np.int32)
+            A_, F_, V_ = self._comp_table([p for p, _ in ulist])
+            ct = ComponentHook(A_, F_, V_, up_(sel), up_(up_a[rb_[sel]].astype(np.int32)), self.layer, m.lspec.heads,
+                               m.spec.eps, out=flat[flat.numel() - n_ct:], sel_host=ct_rows)
+            hooks = {l: list(hooks.get(l, ())) + ([ct] if l in (ct.first, ct.last) else [])
+                     for l in set(hooks) | {ct.first, ct.last}}
+            self.stats["comp_rows"] = self.stats.get("comp_rows", 0) + len(ct_rows)
+            res["_comp"] = ct_dims
         if shift or movers:
             # output shift / movers: tail row (cell, t) is compared with its pair's unedited row t.  ``src`` already
             # names that row in the concatenation of the pairs' rows; per head sub-chunk the distinct baseline rows and
@@ -680,7 +721,7 @@ class ReadoutMixin:
                 res["_movers"] = (Ms, Km, Tm)
         try:
             self._tf_chunks(chunks, streams, tab_d, tab_off, pos_d, slot_d, tgt_d, src_d, H, ws_rows, step, hooks,
-                            nxt, ns, nt, ro, sh, tr)
+                            nxt, ns, nt, ro, sh, tr, ct)
         finally:
             for hk in splice:
                 hk.use_table(None)
@@ -698,13 +739,15 @@ class ReadoutMixin:
         return res
 
     def _tf_chunks(self, chunks, streams, tab_d, tab_off, pos_d, slot_d, tgt_d, src_d, H, ws_rows, step, hooks,
-                   nxt, ns, nt, ro=None, sh=None, tr=None) -> None:
+                   nxt, ns, nt, ro=None, sh=None, tr=None, ct=None) -> None:
         """The packed forwards + vocab heads of :meth:`_tf_launch`, chunk by chunk.  ``ro`` (output readout): the rows'
         tracked ids ``[M, K]`` and the ``[M, K]`` log-prob / rank outputs of the tracking head.  ``sh`` (output
         shift): the pairs' unedited final-normed rows, per head sub-chunk its distinct baseline rows and the rows'
         indices into them, and the ``[M]`` KL outputs.  ``tr`` (layer trace): the launch's trace hook, already listed
-        in ``hooks``; it is told every chunk's row window."""
+        in ``hooks``; it is told every chunk's row window.  ``ct`` (component trace): likewise, and listed as the
+        sub-hook of every later block."""
         m, dev = self.m, self.dev
+        extra = {"sub_hooks": {l: [ct.sub] for l in ct.layers}} if ct is not None else {}
 
         def shift_rows(lg, a, e):
             # the sub-chunk's distinct baseline rows through the same unembedding (whole 256-row tiles), then one pass
@@ -743,8 +786,10 @@ class ReadoutMixin:
                     hin[Mc:].zero_()
                 if tr is not None:
                     tr.use_rows(c0, c1, Mp)
+                if ct is not None:
+                    ct.use_rows(c0, c1, Mp)
                 x = m.forward_packed(None, cp, cs, blk, self.gen.cache, hooks, ws=ws, resume_after=self.layer,
-                                     h_in=hin, prefix_kv=self.pair_kv if self.tf_prefix else None)
+                                     h_in=hin, prefix_kv=self.pair_kv if self.tf_prefix else None, **extra)
                 for q0 in range(0, Mc, step):
                     q1 = min(Mc, q0 + step)
                     if getattr(m, "head_path", False):
@@ -784,10 +829,17 @@ class ReadoutMixin:
 
         m, dev = self.m, self.dev
         # (the output movers use the output shift's baseline side: the kept final-normed rows)
-        shift, trace = self.output_shift or self.output_movers, self.layer_trace
+        shift, trace, comp = self.output_shift or self.output_movers, self.layer_trace, self.component_trace
         stale = lambda v, p: v is None or v[0] is not p.resid      # noqa: E731
         need = [(p, s) for p, s in zip(upairs, slots)
-                if ((shift and stale(p.x_base, p)) or (trace and stale(p.z_base, p))) and p.resid.shape[0]]
+                if ((shift and stale(p.x_base, p)) or (trace and stale(p.z_base, p))
+                    or (comp and stale(p.c_base, p))) and p.resid.shape[0]]
+        if comp:
+            cdim = lambda k: (m.spec.layers - 1 - self.layer, k, 2, m.lspec.heads)      # noqa: E731
+            for p in upairs:                 # an empty response has no selected rows
+                if not p.resid.shape[0] and stale(p.c_base, p):
+                    p.c_base = (p.resid, np.zeros(0, np.int64)) + tuple(
+                        t.numpy() for t in ComponentHook.split(torch.zeros(0), *cdim(0)))
         if trace:
             Lt, Tt = m.spec.layers - self.layer, self._n_trace
             for p in upairs:                 # an empty response has an empty trace
@@ -822,11 +874,44 @@ class ReadoutMixin:
                                float(m.spec.final_softcap or 0.0))
                 tr.use_rows(0, rows, Mp)
                 hooks = {l: [tr] for l in tr.layers}
+            ct, extra = None, {}
+            if comp:
+                # component trace: every spike of a pair and the row behind it, for all the pair's cells
+                tsel, r0 = [], 0
+                for p, _ in grp:
+                    n = p.resid.shape[0]
+                    tsel.append(np.asarray(sorted({u for t in p.spikes_rel if t < n for u in (t, t + 1) if u < n}),
+                                           np.int64))
+                    r0 += n
+                offs = np.concatenate([[0], np.cumsum([p.resid.shape[0] for p, _ in grp])])
+                sel = np.concatenate([t + offs[j] for j, t in enumerate(tsel)]).astype(np.int32)
+                sblk = np.repeat(np.arange(len(grp), dtype=np.int32), [len(t) for t in tsel])
+                A_, F_, V_ = self._comp_table([p for p, _ in grp])
+                ct = ComponentHook(A_, F_, V_, _h2d(sel, dev).to(dev, non_blocking=True),
+                                   _h2d(sblk, dev).to(dev, non_blocking=True), self.layer, m.lspec.heads, m.spec.eps,
+                                   sel_host=sel.tolist())
+                ct.use_rows(0, rows, Mp)
+                hooks = {l: list((hooks or {}).get(l, ())) + ([ct] if l in (ct.first, ct.last) else [])
+                         for l in set(hooks or {}) | {ct.first, ct.last}}
+                extra = {"sub_hooks": {l: [ct.sub] for l in ct.layers}}
             x = m.forward_packed(None, _h2d(pos, dev).to(dev, non_blocking=True),
                                  _h2d(slot, dev).to(dev, non_blocking=True),
                                  _h2d(packed_blocks(seqs, rpb), dev).to(dev, non_blocking=True), self.gen.cache, hooks,
                                  ws=ws, resume_after=self.layer, h_in=hin,
-                                 prefix_kv=self.pair_kv if self.tf_prefix else None)
+                                 prefix_kv=self.pair_kv if self.tf_prefix else None, **extra)
+            if comp:
+                if dev.type == "cuda":
+                    ch = torch.empty(ct.out.shape, dtype=torch.float32, pin_memory=True)
+                    ch.copy_(ct.out, non_blocking=True)
+                else:
+                    ch = ct.out
+                parts = ComponentHook.split(ch, *cdim(len(sel)))         # views of the host copy, sliced per pair
+                i0 = 0
+                for (p, _), ts in zip(grp, tsel):
+                    i1 = i0 + len(ts)
+                    p.c_base = (p.resid, ts, parts[0][:, i0:i1], parts[1][i0:i1], parts[2][i0:i1], parts[3][i0:i1])
+                    i0 = i1
+                self.stats["comp_base_rows"] = self.stats.get("comp_base_rows", 0) + len(sel)
             xs = x[:rows].clone() if shift else None
             zs = None
             if trace:
@@ -847,7 +932,7 @@ class ReadoutMixin:
                 r0 += n
             if shift:
                 self.stats["shift_base_pass_rows"] = self.stats.get("shift_base_pass_rows", 0) + rows
-        if trace and sync and dev.type == "cuda":
+        if (trace or comp) and sync and dev.type == "cuda":
             torch.cuda.current_stream(dev).synchronize()
         if not shift:
             return None
@@ -936,6 +1021,106 @@ class ReadoutMixin:
                "top_gainer": min(tot, key=lambda c: (-tot[c], c)) if tot else -1}
         if donor is not None:
             out["donor_in_gainers"] = in_don / len(sp) if sp else 0.0
+        return out
+
+    def _comp_table(self, upairs: Sequence[Pair]):
+        """Component trace: the launch's tables ``A [Lc, U, 2, heads * head_dim]``, ``F [Lc, U, 2, D]`` and
+        ``Vd [U, 2, D]`` (``interp.edits.component_tables``), one block per pair: column 0 is the pair's secret (the
+        trace's column 0), column 1 its donor word's secret for a pair with swap cells and a zero row otherwise.  A
+        pair's block is built once per runner, in fp64 and rounded once, so its bits never depend on which pairs share
+        its launch."""
+        cache = self.__dict__.setdefault("_comp_blocks", {})
+        out = []
+        for p in upairs:
+            dw = getattr(self, "_pair_donor", {}).get(id(p))
+            ids = [int(p.track[0])] + ([int(p.track[p.extra[dw]])] if dw is not None and dw in p.extra else [])
+            blk = cache.get(tuple(ids))
+            if blk is None:
+                blk = cache[tuple(ids)] = tuple(t.to(self.dev) for t in component_tables(self.m, self.layer, ids, 2))
+            out.append(blk)
+        return (torch.stack([b[0] for b in out], 1).contiguous(), torch.stack([b[1] for b in out], 1).contiguous(),
+                torch.stack([b[2] for b in out], 0).contiguous())
+
+    def _comp_base(self, p: Pair, sp: List[int]) -> dict:
+        """The baseline side of a pair's component fields in logit units, computed once per pair from ``Pair.c_base``:
+        the row of every selected response index, the float64 slabs over the pair's own ``rho_f`` and the
+        ``comp_base_spike`` matrix."""
+        import math
+
+        cb = p.c_base
+        if len(cb) == 7:
+            return cb[6]
+        _, bt, bcomp, bdir, btot, brho = cb
+        H, Lc = self.m.lspec.heads, self.m.spec.layers - 1 - self.layer
+        brf = np.asarray(brho, dtype=np.float64)
+        k = len(bt)
+        d = {"idx": {int(t): i for i, t in enumerate(bt.tolist())},
+             "comp": (np.asarray(bcomp, dtype=np.float64) / brf[None, :, None, None] if k
+                      else np.zeros((Lc, 0, 2, H + 1))),
+             "direct": np.asarray(bdir, dtype=np.float64) / brf[:, None] if k else np.zeros((0, 2)),
+             "total": np.asarray(btot, dtype=np.float64) if k else np.zeros((0, 2))}
+        rows = [d["idx"][t] for t in sp]
+        den = len(sp)
+        d["spike"] = [[math.fsum(v) / den if den else 0.0 for v in blk]
+                      for blk in d["comp"][:, rows, 0, :].transpose(0, 2, 1).tolist()]
+        p.c_base = cb + (d,)
+        return d
+
+    def _comp_fields(self, p: Pair, i0: int, ts: np.ndarray, c: Optional[tuple], swap: bool) -> dict:
+        """Record fields of the component trace for a cell whose selected tail rows are response indices ``ts`` (its
+        spikes ``t >=`` its first effective edit and the rows ``t + 1`` inside its tail), rows ``i0 ..`` of the
+        launch's slabs ``c = (comp [Lc, Ms, 2, heads + 1], direct, total, rho_f)``.  Everything is in logit units:
+        the edited run over its own ``rho_f``, the pair's unedited pass (``Pair.c_base``) over its own, and the
+        difference of the two taken here in float64, so a row no edit reached differs by exactly 0.  ``Lc`` is blocks
+        ``l + 1 .. layers - 1``, the components ``h0 .. h{heads-1}``, then ``mlp``.  ``comp_dz_spike`` /
+        ``comp_dz_next`` are means over the pair's spikes of the edited row itself and of the row right behind it (spikes before the
+        first effective edit, and rows outside the tail, contribute 0; the denominator is the pair's spike count, as
+        for ``trace_dz_spike`` and ``kl_out_spike_mean``); ``comp_base_spike`` is the baseline's own value;
+        ``comp_attn_dz_spike`` / ``comp_mlp_dz_spike`` the heads' sum and the MLP per block;
+        ``comp_direct_dz_spike`` / ``comp_total_dz_spike`` the direct term at block ``l`` and ``z_pre`` of the last
+        block, so ``direct + sum(comp_dz_spike)`` can be checked against the total; ``comp_top_spike`` the largest
+        ``|comp_dz_spike|`` as ``[block, name, value]``; swap cells also get ``comp_dz_donor_spike`` (column 1).  The
+        sums are exactly rounded (``math.fsum``)."""
+        import math
+
+        H = self.m.lspec.heads
+        Lc = self.m.spec.layers - 1 - self.layer
+        n = len(p.resp)
+        sp = [t for t in p.spikes_rel if t < n]
+        den = len(sp)
+        base = self._comp_base(p, sp)
+        bidx, bc, bd, bz = base["idx"], base["comp"], base["direct"], base["total"]
+        k = len(ts)
+        tl = ts.tolist()
+        if k and c is not None:
+            rf = np.asarray(c[3][i0:i0 + k], dtype=np.float64)
+            ec = np.asarray(c[0][:, i0:i0 + k], dtype=np.float64) / rf[None, :, None, None]
+            ed = np.asarray(c[1][i0:i0 + k], dtype=np.float64) / rf[:, None]
+            ez = np.asarray(c[2][i0:i0 + k], dtype=np.float64)
+            at = [bidx[t] for t in tl]
+            dc, dd, dz = ec - bc[:, at], ed - bd[at], ez - bz[at]
+        else:
+            dc, dd, dz = np.zeros((Lc, 0, 2, H + 1)), np.zeros((0, 2)), np.zeros((0, 2))
+        eidx = {t: i for i, t in enumerate(tl)}
+        # the tail's selected rows start at its first effective spike: every spike among them is an edited one
+        hit = [eidx[t] for t in sp if t in eidx]
+        nxt = [eidx[t + 1] for t in sp if t in eidx and t + 1 in eidx]
+        mean = lambda v: math.fsum(v) / den if den else 0.0        # noqa: E731
+        # [Lc][heads + 1] of exactly rounded sums over the listed rows (one transposed copy, then plain lists)
+        mat = lambda a, rows, col: [[mean(v) for v in blk]          # noqa: E731
+                                    for blk in a[:, rows, col, :].transpose(0, 2, 1).tolist()]
+        out = {"comp_dz_spike": mat(dc, hit, 0), "comp_dz_next": mat(dc, nxt, 0),
+               "comp_base_spike": base["spike"],
+               "comp_direct_dz_spike": mean(dd[hit, 0].tolist()), "comp_total_dz_spike": mean(dz[hit, 0].tolist())}
+        out["comp_attn_dz_spike"] = [math.fsum(r[:H]) for r in out["comp_dz_spike"]]
+        out["comp_mlp_dz_spike"] = [r[H] for r in out["comp_dz_spike"]]
+        names = [f"h{j}" for j in range(H)] + ["mlp"]
+        top = max(((abs(v), -kk, -j) for kk, r in enumerate(out["comp_dz_spike"]) for j, v in enumerate(r)),
+                  default=(0.0, 0, 0))
+        kk, j = -top[1], -top[2]
+        out["comp_top_spike"] = [self.layer + 1 + kk, names[j], out["comp_dz_spike"][kk][j] if Lc else 0.0]
+        if swap:
+            out["comp_dz_donor_spike"] = mat(dc, hit, 1)
         return out
 
     def _trace_table(self, upairs: Sequence[Pair]) -> torch.Tensor:

@@ -90,6 +90,11 @@ class Pair:
     # logits of ``track`` at blocks l .. layers - 1 of the same unedited pass) -- the baseline side of the cells'
     # ``trace_*`` fields (ReadoutMixin._shift_base)
     z_base: Optional[tuple] = None
+    # intervention.component_trace only: (the ``resid`` they were computed from, the selected response rows ``t``
+    # [k] -- every spike and the row behind it -- and the host copies ``comp [Lc, k, T, heads + 1]``, ``direct [k, T]``,
+    # ``total [k, T]``, ``rho_f [k]`` of the same unedited pass) -- the baseline side of the cells' ``comp_*`` fields
+    # (ReadoutMixin._shift_base)
+    c_base: Optional[tuple] = None
 
     def ro_order(self) -> List[int]:
         """Column order of ``track`` in the tracking head's id table (output readout): the secret's two forms, the

@@ -10,6 +10,9 @@
 * ``fig5_collateral.png`` — output shift (``intervention.output_shift``), only for sweeps run with it: the KL between
   the baseline's and the edited next-token distribution vs budget / rank, targeted against its controls; with the
   output readout also the specificity plane (Δ log-prob of the secret against that KL);
+* ``fig8_components.png`` — component trace (``intervention.component_trace``), only for sweeps run with it: a heatmap
+  of block × component (heads, then the MLP) of the change of each later component's direct contribution to the
+  secret's lens logit, the targeted method at its largest budget beside its random control.
 * ``fig6_layer_trace.png`` — layer trace (``intervention.layer_trace``), only for sweeps run with it: the change of the
   secret's capped lens logit at the edited rows against the block it is read at, one line per budget, targeted
   against its controls;
@@ -342,6 +345,46 @@ def movers_curves(summary: Dict, path: str) -> None:
     plt.close(fig)
 
 
+def component_heatmaps(summary: Dict, path: str) -> None:
+    """Component trace (intervention.component_trace): the mean ``comp_dz_spike`` -- the change of each later
+    component's direct contribution to the secret's lens logit at the edited rows, edited minus baseline -- as a
+    heatmap of block x component (heads, then the MLP): per kind (SAE / subspace) the targeted method at its largest
+    budget beside its random control at the same budget, on one symmetric colour scale.  One bright cell is one head
+    re-writing the secret; an even wash is a distributed repair."""
+    curves = [c for c in summary["curves"] if "comp_dz_spike" in c]
+    cfg = summary.get("config", {})
+    blocks = cfg.get("comp_blocks") or list(range(len(curves[0]["comp_dz_spike"])))
+    names = cfg.get("comp_names") or [str(j) for j in range(len(curves[0]["comp_dz_spike"][0]))]
+    panels = []
+    for kind in ("sae", "proj"):
+        tg = [c for c in curves if c["method"] in (f"{kind}_targeted", f"{kind}_swap")]
+        if not tg:
+            continue
+        top = max(tg, key=lambda c: (c["budget"], c["method"].endswith("targeted")))
+        panels.append(top)
+        ctl = [c for c in curves if c["method"] == f"{kind}_random" and c["budget"] == top["budget"]]
+        panels += ctl[:1]
+    panels = panels or curves[:2]
+    vmax = max((abs(v) for c in panels for row in c["comp_dz_spike"] for v in row), default=0.0) or 1.0
+    fig, axes = plt.subplots(1, len(panels), figsize=(1.5 + 3.6 * len(panels), 1.6 + 0.28 * len(blocks)),
+                             squeeze=False)
+    im = None
+    for ax, c in zip(axes[0], panels):
+        im = ax.imshow(c["comp_dz_spike"], cmap="RdBu_r", vmin=-vmax, vmax=vmax, aspect="auto")
+        ax.set_xticks(range(len(names)))
+        ax.set_xticklabels(names, fontsize=6, rotation=90)
+        ax.set_yticks(range(len(blocks)))
+        ax.set_yticklabels(blocks, fontsize=6)
+        ax.set_xlabel("component")
+        ax.set_ylabel("block")
+        ax.set_title(f"{c['method']} {c['budget']} (n = {c['n']})", fontsize=8)
+    if im is not None:
+        fig.colorbar(im, ax=list(axes[0]), shrink=0.8, label="Δ direct contribution to the secret's lens logit")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    fig.savefig(path, dpi=150)
+    plt.close(fig)
+
+
 def baselines_table(rows: Dict[str, Dict[str, float]], path: str) -> None:
     lines = ["method,pass@10,majority@10,accuracy"]
     for name, m in rows.items():
@@ -390,6 +433,10 @@ def make_report(results_dir: str, out_dir: str) -> List[str]:
             if any("movers_up_share" in c for c in s["curves"]):   # only sweeps run with the output movers
                 p = os.path.join(out_dir, f"fig7_movers_{tag}.png")
                 movers_curves(s, p)
+                made.append(p)
+            if any("comp_dz_spike" in c for c in s["curves"]):     # only sweeps run with the component trace
+                p = os.path.join(out_dir, f"fig8_components_{tag}.png")
+                component_heatmaps(s, p)
                 made.append(p)
             if s.get("baselines"):
                 from .dashboards import write_latent_dashboard
